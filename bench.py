@@ -12,11 +12,18 @@ no data-path collective; the only RCCL traffic is the final all-gather of (log_l
 the arg-max (tools/parallel.hpp:169-191 `par::max`), issued inside the timed region.
 value = (N ranks x K steps) / max-over-ranks time.  Scaling is weak.
 
-Besides the headline (`value`: X resident in HBM when the timed region starts) the line carries
-`value_incl_h2d` (the same step with gpe_set_data — 196 KB of X + 32 KB of obs_mean over PCIe — inside the timed
-region: the reference's compute() includes that ingest, gp.hpp:88-116), `config4` (BASELINE configs[3] as written:
-8 independent GPs of N=2048 per GPU through ONE gpe_batch_compute, aggregated over the ranks => 64 GPs on 8 GPUs),
-`roofline`, and two CPU baselines timed on this box (single-core port; all-core numpy + LAPACK).
+A plain run times the headline only (`value`: X resident in HBM when the timed region starts): set-up, warm-up, the
+K timed steps, the outputs of the last step if --dump-outputs is given, the JSON line.  Everything else runs only with
+--full (trimmed by --no-cpu-baseline / --no-roofline / --no-extras / --headline-only): `value_incl_h2d` (the same step
+with gpe_set_data — 196 KB of X + 32 KB of obs_mean over PCIe — inside the timed region: the reference's compute()
+includes that ingest, gp.hpp:88-116), `config4` (BASELINE configs[3] as written: 8 independent GPs of N=2048 per GPU
+through ONE gpe_batch_compute, aggregated over the ranks => 64 GPs on 8 GPUs), `config3_sharded` (world > 1),
+`roofline` and the per-kernel figures, concurrent handles, the secondary configs (`extras`), and two CPU baselines timed
+on this box (single-core port; all-core numpy + LAPACK).
+
+--dump-outputs DIR (rank 0): what the last timed step computed, as float64 .npy files — `log_lik` (1,), `alpha` (N, P) and
+`L_rows` (256, N): the lower-triangular factor's rows at a fixed seeded sample of row indices (the whole factor is 128 MB).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -345,6 +352,10 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=N_C2, help="override N (debug only; invalidates the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: value_incl_h2d, config4, config3_sharded, roofline and per-kernel figures, concurrent "
+                         "handles, the secondary configs and the CPU baselines (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--headline-only", action="store_true", help="profiling runs: only the N=4096 evaluation loop (no H2D variant, no config 4)")
@@ -358,6 +369,8 @@ def main():
                     help="collective backend for --gpus > 1: nccl (= RCCL over xGMI, the default) or gloo (CPU tensors for the two "
                          "collectives; lets several ranks share one visible GPU: tests/test_gpu_configs.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -468,8 +481,17 @@ def main():
                   "p90_ms": float(np.percentile(per, 90)), "block_ms_per_step": blocks,
                   "value_from_median_step": world * 1e3 / float(np.median(per))}
 
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed step holds after its last call: log-lik, alpha and (a seeded row sample of) L
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        rows = np.sort(np.random.default_rng(0).choice(N, size=min(256, N), replace=False))
+        np.save(dump / "log_lik.npy", np.array([ll], dtype=np.float64))
+        np.save(dump / "alpha.npy", np.ascontiguousarray(h.get_alpha(), dtype=np.float64))
+        np.save(dump / "L_rows.npy", np.ascontiguousarray(np.tril(h.get_L())[rows], dtype=np.float64))
+
     value_incl_h2d, config4 = None, None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         # the same step with the host -> device ingest of (X, obs_mean) inside: gp.hpp:88-116 as the reference times it
         n_h2d = max(5, args.steps // 2)
         sync()
@@ -515,7 +537,7 @@ def main():
                    "tflops": world * G4 * reps4 / dt4 * (N4 ** 3 / 3.0 + 2.0 * N4 * N4) / 1e12, "best_log_lik": float(best4[0])}
 
     config3_sharded = None
-    if not args.headline_only and dist is not None:
+    if args.full and not args.headline_only and dist is not None:
         # BASELINE configs[2] across ranks — SURVEY §8(e)'s second shard axis (multi_gp.hpp:191-195, tools/parallel.hpp:138-201: the
         # reference's parallel query): every rank factors its OWN replica of the N = 16384 Matern-5/2 GP (31 ms — cheaper than
         # broadcasting a 2 GiB factor over xGMI), answers row_slice(M, rank, world) of the 100 000 points with one
@@ -594,7 +616,7 @@ def main():
         "handover_reruns": h.handover_reruns(), "flow_retries": h.flow_retries(),
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # dominant kernel: the Cholesky trailing update (k_gemm_glds / k_gemm_glds64 / k_gemm4, fp64 MFMA).  HIP events on
         # the handle's own stream around every launch of it (profiling mode: every phase alone on the chip), outside the
         # timed region.  Round 4: ALL of the factorisation is accounted for — the update launch(es), the two data-flow
@@ -718,7 +740,7 @@ def main():
         out["box_probe"] = box_probe(eng, _capi, O, local_rank)
         out["phases_us_per_step_profiled"] = {k: v["us"] for k, v in ph.items()}
 
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         # R independent evaluations in flight from R host threads (the reference runs hyper-parameter restarts concurrently:
         # opt/parallel_repeater.hpp:86-105 under tools::par::max).  Round 4 ordered the data-flow launches of different handles
         # chain behind chain (two at once can starve each other's lowest unfinished workgroup); round 5: while another chain
@@ -767,10 +789,10 @@ def main():
                 hr.close()
         out["concurrent_evaluations_per_s"] = conc
 
-    if rank == 0 and world == 1 and not args.no_extras and not args.headline_only and N == N_C2:
+    if rank == 0 and world == 1 and args.full and not args.no_extras and not args.headline_only and N == N_C2:
         out.update(extras(eng, _capi, O, local_rank, args.steps))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # CPU side-by-side: the oracle (C restatement of the reference's path, 1 thread = the
         # reference's default: one GP::compute is single-threaded) on a bounded sample.
         from oracle import binding as OB  # the checker, cpu_baseline leg only

@@ -73,7 +73,7 @@ def ref_available() -> bool:
 def load_ref():
     if "ref" not in _libs:
         if REFERENCE_SRC.exists():  # (re)build where the reference sources are; a no-op when up to date
-            subprocess.check_call(["make", "-s", "-C", str(HERE / "ref_build")])
+            subprocess.check_call(["make", "-s", "-C", str(HERE / "ref_build"), "../_ref/libref.so"])
         if not REF_SO.exists():
             raise FileNotFoundError(f"{REF_SO} is missing and /root/reference is not here to build it")
         cd = C.CDLL(str(REF_SO), mode=getattr(os, "RTLD_NOW", 2) | getattr(os, "RTLD_LOCAL", 0))

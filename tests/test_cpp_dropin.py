@@ -66,9 +66,11 @@ def test_dropin_cases_on_device(virtual_devices, min_n):
 def test_dropin_with_limbos_own_tree_behind_it():
     """INTEGRATION.md's include-path switch with /root/reference/src behind the drop-in: limbo's opt::GridSearch /
     RandomPoint / tools over the device model in a boptimizer.hpp-shaped loop (tests/cpp/test_mixed_tree.cpp).
-    The binary is built where the reference sources are and travels with the snapshot."""
+    The binary is built where the reference sources are, beside libref.so (oracle/ref_build/Makefile -> oracle/_ref/)."""
     _build()
-    exe = CPP / "test_mixed_tree"
+    # (a no-op where the reference sources are absent: a prebuilt binary is used)
+    subprocess.check_call(["make", "-C", str(ROOT / "oracle" / "ref_build"), "../_ref/test_mixed_tree"], stdout=subprocess.DEVNULL)
+    exe = ROOT / "oracle" / "_ref" / "test_mixed_tree"
     if not exe.exists():
         pytest.skip("test_mixed_tree was not built (no /root/reference at build time)")
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)

@@ -32,9 +32,9 @@ f=$(find /tmp/p_FETCH_SIZE -name "*.db" | head -1); w=$(find /tmp/p_WRITE_SIZE -
 python $root/tools/pmc_summary.py $f $w $m > $out/${tag}_pmc_bench.json   # (bench.py reads profiles/r05_pmc_bench.json: roofline.traffic)
 { echo "# rocprofv3 --pmc passes (GPE_LOOKAHEAD=0 GPE_TAIL_GEN=0) over: bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-roofline --headline-only"; echo "# separate passes: FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F64   (FETCH_SIZE / WRITE_SIZE in KiB per dispatch; FETCH to be doubled, MI355X_MICROARCH.md)"; KSTATS_GRID=1 python $root/tools/kpmc.py $f $w $m; } > $out/${tag}_pmc_bench_n4096.txt
 cd $root
-python bench.py > $out/${tag}_bench_n4096.json 2> $out/bench.err
+python bench.py --full > $out/${tag}_bench_n4096.json 2> $out/bench.err
 if [ -z "${SKIP_TESTS:-}" ]; then
-{ python -m pytest tests -m gpu -q 2>&1 | tail -5; tests/cpp/test_gp_dropin; LIMBO_AMD_MIN_N_FOR_GPU=0 tests/cpp/test_gp_dropin | tail -3; tests/cpp/test_mixed_tree; } > $out/${tag}_s1_gpu_tests.log 2>&1
+{ python -m pytest tests -m gpu -q 2>&1 | tail -5; tests/cpp/test_gp_dropin; LIMBO_AMD_MIN_N_FOR_GPU=0 tests/cpp/test_gp_dropin | tail -3; oracle/_ref/test_mixed_tree; } > $out/${tag}_s1_gpu_tests.log 2>&1
 fi
 # the production schedule traced by the library itself (every launch with its own start/stop events)
 python tools/trace_eval.py compute 4096 > $out/${tag}_production_timeline.txt 2> $out/trace.err
