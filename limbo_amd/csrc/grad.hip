@@ -383,8 +383,10 @@ __global__ __launch_bounds__(256) void k_sym_colscale(const double* __restrict__
 }
 __global__ void k_scale_vec(double* __restrict__ g, int n, double f)
 {
-    if ((int)threadIdx.x < n)
-        g[threadIdx.x] *= f;
+    // (n = n_theta + noise reaches GPE_MAX_THETA + 1 = 65, one more than the wave: with `if (threadIdx.x < n)` the LOO
+    // gradient's noise entry stayed unscaled, half its value, at 64 parameters with optimize_noise)
+    for (int t = (int)threadIdx.x; t < n; t += (int)blockDim.x)
+        g[t] *= f;
 }
 
 void launch_loo_prep(hipStream_t s, const double* Kinv, int64_t ldk, int64_t N, const double* alpha, int64_t lda, int P,

@@ -19,6 +19,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 from oracle import np_oracle as O  # noqa: E402
+from tests import high_dim as HD  # noqa: E402
 
 OUT = ROOT / "tests" / "golden"
 
@@ -53,6 +54,24 @@ def small_cases():
         Xq = rng.uniform(-1.8, 1.8, size=(7, D))
         Xq[0] = X[0]  # a query ON a training point (sigma^2 cancellation / clamp path)
         cases.append(dict(kind=kind, X=X, Y=Y, obs_mean=om, mean=mean, theta=theta, noise=noise,
+                          optimize_noise=on, Xq=Xq, lam=lam))
+    # above 16 input dimensions, built as tests/high_dim.py builds them (length scales ~ sqrt(D), every dimension its own
+    # weight, the last one the heaviest) from the same stream; appended, so that the cases above keep their random draws.
+    # (tests/test_high_dim_problems.py checks these files' gradients per component as well)
+    #             kind        N   D   P  noise optimize_noise  k
+    hd_specs = [(O.SE_ARD, 40, 17, 1, 0.01, False, 0),       # k_build / k_grad_tiles <32>
+                (O.SE_ARD, 34, 62, 1, 0.01, True, 0),        # the top of the range: 63 theta, 64 gradient entries
+                (O.MATERN52, 40, 40, 2, 0.02, True, 0),      # <64>
+                (O.MATERN32, 36, 33, 1, 0.01, False, 0),     # <64>
+                (O.EXP, 32, 62, 1, 0.01, True, 0),           # <64>
+                (O.SE_ARD, 40, 16, 1, 0.02, True, 1),        # kp.D = 17: the inputs fit <16>, the kernel runs <32>
+                (O.SE_ARD, 34, 31, 2, 0.01, False, 1),       # kp.D = 32
+                (O.SE_ARD, 40, 21, 1, 0.02, True, 2)]        # 64 theta (GPE_MAX_THETA), 65 gradient entries
+    for kind, N, D, P, noise, on, lam in hd_specs:
+        pb = HD.problem(kind, N, D, P=P, k=lam, seed=rng, noise=noise)
+        Xq = rng.uniform(0, 1, size=(7, D)) * pb.X.max(axis=0)
+        Xq[0] = pb.X[0]
+        cases.append(dict(kind=kind, X=pb.X, Y=pb.Y, obs_mean=pb.obs_mean, mean=pb.mean, theta=pb.theta, noise=noise,
                           optimize_noise=on, Xq=Xq, lam=lam))
     return cases
 
