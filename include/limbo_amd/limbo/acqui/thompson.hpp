@@ -1,0 +1,60 @@
+// limbo/acqui/thompson.hpp — Thompson sampling over a candidate set: batch proposals from ONE model state.
+// Not in the reference (its acquisition functors score one point from the marginals, src/limbo/acqui/ucb.hpp:77-95); built
+// on the joint posterior of model::GP (query_joint / sample, include/gpe_joint.h): q independent function draws over the
+// candidates, each proposes its own maximiser.  A `boptimizer`-shaped loop evaluates the q proposals, add_sample()s them and
+// asks again.
+#ifndef LIMBO_AMD_ACQUI_THOMPSON_HPP
+#define LIMBO_AMD_ACQUI_THOMPSON_HPP
+#include <cstdint>
+#include <type_traits>
+#include <vector>
+
+#include <Eigen/Core>
+
+namespace limbo_amd {
+    /// the default aggregator of limbo's optimisers (bayes_opt/bo_base.hpp: FirstElem): the first output
+    struct FirstElem {
+        typedef double result_type;
+        double operator()(const Eigen::VectorXd& x) const { return x(0); }
+    };
+
+    /// The indices (into `candidates`) that maximise q independent posterior draws of afun(f(.)); the lowest index on exact
+    /// ties.  Draw s uses the standard normals Model::standard_normals(M q dim_out, seed) in sample()'s layout, so the result
+    /// equals the arg-max over model.sample(candidates, q, seed, jitter).  With one output and the FirstElem aggregator the
+    /// arg-max runs on the device and the draws never leave it; otherwise they are aggregated on the host.
+    /// jitter: as for sample() — the kernel's noise, or a small value (1e-8 .. 1e-6) for draws of f.
+    template <typename Model, typename AggregatorFunction = FirstElem>
+    std::vector<int64_t> thompson_batch(const Model& model, const std::vector<Eigen::VectorXd>& candidates, int q,
+        const AggregatorFunction& afun = AggregatorFunction(), uint64_t seed = 0, double jitter = 1e-6)
+    {
+        const int64_t M = candidates.size();
+        const int P = model.dim_out();
+        std::vector<int64_t> out;
+        if (M == 0 || q <= 0)
+            return out;
+        const std::vector<double> Z = Model::standard_normals((size_t)M * (size_t)q * (size_t)P, seed);
+        if (P == 1 && std::is_same<AggregatorFunction, FirstElem>::value) {
+            std::vector<double> fmax;
+            model.sample_argmax(candidates, Z, q, jitter, out, fmax);
+            return out;
+        }
+        const std::vector<Eigen::MatrixXd> F = model.sample(candidates, Z, q, jitter);
+        for (int s = 0; s < q; ++s) {
+            int64_t best = 0;
+            double vbest = 0.0;
+            for (int64_t m = 0; m < M; ++m) {
+                Eigen::VectorXd row(P);
+                for (int p = 0; p < P; ++p)
+                    row(p) = F[(size_t)s](m, p);
+                const double v = afun(row);
+                if (m == 0 || v > vbest) {
+                    vbest = v;
+                    best = m;
+                }
+            }
+            out.push_back(best);
+        }
+        return out;
+    }
+} // namespace limbo_amd
+#endif

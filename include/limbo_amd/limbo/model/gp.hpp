@@ -40,6 +40,7 @@
 #include <iostream>
 #include <limits>
 #include <mutex>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -59,6 +60,7 @@
 #include <limbo/tools/parallel.hpp>
 
 #include "../../../gpe.h"
+#include "../../../gpe_joint.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -289,6 +291,78 @@ namespace limbo {
                         mu_out(m, p) = kta[(size_t)(m + M * p)] + mv(p);
                     sigma_sq(m) = _finish_sigma(var[(size_t)m]) + _kernel_function.noise();
                 }
+            }
+
+            /// Addition (include/gpe_joint.h): the JOINT posterior of a batch — mu (M x dim_out, the mean functor added, as
+            /// query_batch) and the full predictive covariance cov (M x M, symmetric; one matrix serves all outputs):
+            /// cov(a, b) = k(v_a, v_b) - (L^-1 k_a).(L^-1 k_b) + jitter [a == b], the kernel WITHOUT noise and without the clamp of
+            /// gp.hpp:621-623, so cov(m, m) == sigma(points[m]) - noise where that is above the clamp.  Runs on the model's home
+            /// device (cov couples the points: the dealing of large query_batch() calls over devices does not apply); no samples:
+            /// the prior; a host-resident model below the batch crossover, and kernels without device code: on the host from
+            /// matrixL() (O(M n^2 + M^2 n) scalar work — slow for large models).
+            void query_joint(const std::vector<Eigen::VectorXd>& points, Eigen::MatrixXd& mu_out, Eigen::MatrixXd& cov, double jitter = 0) const
+            {
+                const int64_t M = points.size();
+                mu_out.resize(M, _dim_out);
+                cov.resize(M, M);
+                if (M == 0)
+                    return;
+                std::vector<double> kta((size_t)(M * _dim_out), 0.0);
+                if (_joint_on_host(M))
+                    _host_joint(points, kta.data(), cov.data(), jitter);
+                else {
+                    const std::vector<double> Xq = _joint_points(points);
+                    _eng.check(gpe_joint_query(_eng.get(), Xq.data(), M, jitter, kta.data(), cov.data(), M), "gpe_joint_query");
+                }
+                for (int64_t m = 0; m < M; ++m) {
+                    Eigen::VectorXd mv = _mean_function(points[m], *this);
+                    for (int p = 0; p < _dim_out; ++p)
+                        mu_out(m, p) = kta[(size_t)(m + M * p)] + mv(p);
+                }
+            }
+
+            /// Addition: n_draws function draws from the joint posterior at `points`, one M x dim_out matrix per draw:
+            /// F_s = m(V) + k(V, X) alpha + chol(cov + jitter I) Z_s with the standard normals Z (M x n_draws x dim_out, point
+            /// fastest, then draw) supplied by the caller: a deterministic function of (model, points, jitter, Z).  jitter = the
+            /// kernel's noise gives draws of noisy observations, a small value draws of f.  Throws std::runtime_error when
+            /// cov + jitter I is not positive definite.
+            std::vector<Eigen::MatrixXd> sample(const std::vector<Eigen::VectorXd>& points, const std::vector<double>& Z, int n_draws, double jitter) const
+            {
+                const int64_t M = points.size();
+                std::vector<double> F((size_t)(M * n_draws * _dim_out));
+                _draws(points, Z, n_draws, jitter, F.data(), nullptr, nullptr);
+                std::vector<Eigen::MatrixXd> out;
+                for (int s = 0; s < n_draws; ++s) {
+                    Eigen::MatrixXd f(M, _dim_out);
+                    for (int p = 0; p < _dim_out; ++p)
+                        for (int64_t m = 0; m < M; ++m)
+                            f(m, p) = F[(size_t)(m + M * (s + (int64_t)n_draws * p))];
+                    out.push_back(f);
+                }
+                return out;
+            }
+            /// ... with Z from std::mt19937_64(seed) through std::normal_distribution, in the order of Z's layout
+            std::vector<Eigen::MatrixXd> sample(const std::vector<Eigen::VectorXd>& points, int n_draws, uint64_t seed, double jitter) const
+            {
+                return sample(points, standard_normals((size_t)points.size() * (size_t)n_draws * (size_t)_dim_out, seed), n_draws, jitter);
+            }
+            static std::vector<double> standard_normals(size_t n, uint64_t seed)
+            {
+                std::mt19937_64 gen(seed);
+                std::normal_distribution<double> nd(0.0, 1.0);
+                std::vector<double> z(n);
+                for (double& v : z)
+                    v = nd(gen);
+                return z;
+            }
+            /// Addition: per draw s and output p the index of the point with the largest value (the lowest one on exact ties) and
+            /// that value, argmax[s + n_draws p] — on the device the draws themselves never leave it (acqui/thompson.hpp)
+            void sample_argmax(const std::vector<Eigen::VectorXd>& points, const std::vector<double>& Z, int n_draws, double jitter,
+                std::vector<int64_t>& argmax, std::vector<double>& fmax) const
+            {
+                argmax.assign((size_t)(n_draws * _dim_out), 0);
+                fmax.assign((size_t)(n_draws * _dim_out), 0.0);
+                _draws(points, Z, n_draws, jitter, nullptr, argmax.data(), fmax.data());
             }
 
             int dim_in() const
@@ -1135,6 +1209,116 @@ namespace limbo {
                 return 1 + (int)_replicas.size();
             }
         protected:
+            // ---- the joint posterior (query_joint, sample) ----
+            bool _joint_on_host(int64_t M) const
+            {
+                if (_samples.size() == 0 || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K)
+                    return true;
+                return _host_mode && M * (int64_t)_samples.size() < (int64_t)limbo_amd::host_batch_crossover();
+            }
+            // row-major points for the engine (a host-resident model first refreshes its device copy)
+            std::vector<double> _joint_points(const std::vector<Eigen::VectorXd>& pts) const
+            {
+                if (_host_mode)
+                    _sync_device_shadow();
+                const int64_t M = pts.size();
+                std::vector<double> Xq((size_t)(M * _dim_in));
+                for (int64_t m = 0; m < M; ++m) {
+                    assert((int)pts[m].size() == _dim_in);
+                    for (int d = 0; d < _dim_in; ++d)
+                        Xq[(size_t)(m * _dim_in + d)] = pts[m](d);
+                }
+                return Xq;
+            }
+            // kta[m + M p], cov (M x M, column-major) on the host: the prior without samples, else from matrixL() and alpha()
+            void _host_joint(const std::vector<Eigen::VectorXd>& pts, double* kta, double* cov, double jitter) const
+            {
+                const int64_t M = pts.size(), n = _samples.size();
+                for (int64_t b = 0; b < M; ++b)
+                    for (int64_t a = b; a < M; ++a) {
+                        const double v = _kernel_function(pts[a], pts[b]) + (a == b ? jitter : 0.0);
+                        cov[a + M * b] = v;
+                        cov[b + M * a] = v;
+                    }
+                if (n == 0) {
+                    if (kta)
+                        std::fill(kta, kta + M * _dim_out, 0.0);
+                    return;
+                }
+                const Eigen::MatrixXd& L = matrixL();
+                const Eigen::MatrixXd& al = alpha();
+                std::vector<double> Ks((size_t)(n * M));
+                for (int64_t m = 0; m < M; ++m)
+                    for (int64_t i = 0; i < n; ++i)
+                        Ks[(size_t)(i + n * m)] = _kernel_function(_samples[i], pts[m]);
+                if (kta)
+                    for (int p = 0; p < _dim_out; ++p)
+                        for (int64_t m = 0; m < M; ++m) {
+                            double s = 0.0;
+                            for (int64_t i = 0; i < n; ++i)
+                                s += Ks[(size_t)(i + n * m)] * al.data()[i + n * p];
+                            kta[m + M * p] = s;
+                        }
+                limbo_amd::host_small::solve_lower(L.data(), n, n, Ks.data(), M, n);
+                for (int64_t b = 0; b < M; ++b)
+                    for (int64_t a = b; a < M; ++a) {
+                        double s = 0.0;
+                        for (int64_t i = 0; i < n; ++i)
+                            s += Ks[(size_t)(i + n * a)] * Ks[(size_t)(i + n * b)];
+                        cov[a + M * b] -= s;
+                        if (a != b)
+                            cov[b + M * a] = cov[a + M * b];
+                    }
+            }
+            // F (M x S x P, may be null), argmax / fmax (S x P, may be null)
+            void _draws(const std::vector<Eigen::VectorXd>& pts, const std::vector<double>& Z, int S, double jitter, double* F, int64_t* argmax,
+                double* fmax) const
+            {
+                const int64_t M = pts.size();
+                const int P = _dim_out;
+                if ((int64_t)Z.size() < M * S * P)
+                    throw std::runtime_error("limbo_amd: sample(): Z must hold points x draws x dim_out standard normals");
+                if (M == 0 || S <= 0)
+                    return;
+                std::vector<double> mq((size_t)(M * P));
+                for (int64_t m = 0; m < M; ++m) {
+                    Eigen::VectorXd mv = _mean_function(pts[m], *this);
+                    for (int p = 0; p < P; ++p)
+                        mq[(size_t)(m + M * p)] = mv(p);
+                }
+                int rc = 0;
+                if (!_joint_on_host(M)) {
+                    const std::vector<double> Xq = _joint_points(pts);
+                    rc = _eng.check(gpe_joint_draws(_eng.get(), Xq.data(), M, jitter, mq.data(), Z.data(), S, F, argmax, fmax), "gpe_joint_draws");
+                }
+                else {
+                    std::vector<double> kta((size_t)(M * P)), C((size_t)(M * M)), f((size_t)M);
+                    _host_joint(pts, kta.data(), C.data(), jitter);
+                    rc = limbo_amd::host_small::llt_lower(C.data(), M, M);
+                    for (int q = 0; q < S * P && rc == 0; ++q) {
+                        const int p = q / S;
+                        const double* z = Z.data() + (int64_t)q * M;
+                        for (int64_t m = 0; m < M; ++m) {
+                            double s = 0.0;
+                            for (int64_t j = 0; j <= m; ++j)
+                                s += C[(size_t)(m + M * j)] * z[j];
+                            f[(size_t)m] = mq[(size_t)(m + M * p)] + (kta[(size_t)(m + M * p)] + s);
+                        }
+                        if (F)
+                            std::copy(f.begin(), f.end(), F + (int64_t)q * M);
+                        int64_t best = 0;
+                        for (int64_t m = 1; m < M; ++m)
+                            if (f[(size_t)m] > f[(size_t)best])
+                                best = m;
+                        if (argmax)
+                            argmax[q] = best;
+                        if (fmax)
+                            fmax[q] = f[(size_t)best];
+                    }
+                }
+                if (rc > 0)
+                    throw std::runtime_error("limbo_amd: sample(): cov + jitter I is not positive definite (pivot " + std::to_string(rc) + "): raise jitter");
+            }
             void _query_one(const Eigen::VectorXd& v, Eigen::VectorXd* kta, double* var) const
             {
                 if (_host_mode) {

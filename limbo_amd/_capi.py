@@ -100,6 +100,12 @@ def _sig(lib, prefix):
             "hbm_stream_peak": [C.c_int, _dp],
             "epoch": [_vp, C.POINTER(C.c_uint64)],
             "xproc_waits": [C.POINTER(_i64)],
+            # include/gpe_joint.h: the joint posterior over a point batch
+            "joint_query": [_vp, _dp, _i64, C.c_double, _dp, _dp, _i64],
+            "joint_draws": [_vp, _dp, _i64, C.c_double, _dp, _dp, C.c_int, _dp, C.POINTER(_i64), _dp],
+            "joint_max_points": [_vp, C.POINTER(_i64)],
+            "joint_phase_ms": [_vp, _dp],
+            "debug_cov_plan": [_i64, _i64, C.c_int, C.POINTER(_i64), _i64],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -318,6 +324,53 @@ class Handle:
                                              _d(var) if want_var else None), "query_batch")
         return kta, var
 
+    # -- the joint posterior over a point batch (include/gpe_joint.h; HIP library only)
+    def joint_query(self, Xq, jitter=0.0, want_mu=True, want_cov=True):
+        """(kta (M x P), cov (M x M, full symmetric, jitter on the diagonal)); either may be None."""
+        Xq = _c(Xq).reshape(-1, self.D)
+        M = Xq.shape[0]
+        kta = np.zeros((M, self.P), order="F") if want_mu else None
+        cov = np.zeros((M, M), order="F") if want_cov else None
+        self._chk(self.lib.fn("joint_query")(self._h, _d(Xq), M, float(jitter), _d(kta) if want_mu else None,
+                                             _d(cov) if want_cov else None, max(M, 1)), "joint_query")
+        return kta, cov
+
+    def joint_draws(self, Xq, Z, jitter, mean_q=None, want_F=True, want_argmax=True):
+        """Z: (M, S, P) standard normals.  Returns (status, F (M, S, P) or None, argmax (S, P) or None, fmax (S, P) or None);
+        status > 0 is the first non-positive pivot of cov + jitter I (the other results are then undefined)."""
+        Xq = _c(Xq).reshape(-1, self.D)
+        M = Xq.shape[0]
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim == 2:
+            Z = Z[:, :, None]
+        assert Z.shape[0] == M and Z.shape[2] == self.P
+        S = Z.shape[1]
+        Zf = _c(Z.reshape(M, S * self.P, order="F"), "F")
+        mq = None
+        if mean_q is not None:
+            mq = _c(np.asarray(mean_q, dtype=np.float64).reshape(M, self.P), "F")
+        F = np.zeros((M, S * self.P), order="F") if want_F else None
+        am = np.zeros(S * self.P, dtype=np.int64) if want_argmax else None
+        fm = np.zeros(S * self.P) if want_argmax else None
+        rc = self._chk(self.lib.fn("joint_draws")(self._h, _d(Xq), M, float(jitter), _d(mq) if mq is not None else None, _d(Zf), S,
+                                                  _d(F) if want_F else None,
+                                                  am.ctypes.data_as(C.POINTER(_i64)) if want_argmax else None,
+                                                  _d(fm) if want_argmax else None), "joint_draws")
+        return (rc, F.reshape(M, S, self.P, order="F") if want_F else None,
+                am.reshape(S, self.P, order="F") if want_argmax else None,
+                fm.reshape(S, self.P, order="F") if want_argmax else None)
+
+    def joint_phase_ms(self):
+        """{Z, cov, chol, draws} of the last joint call in ms (set_profiling(True) first)."""
+        ms = np.zeros(4)
+        self._chk(self.lib.fn("joint_phase_ms")(self._h, _d(ms)), "joint_phase_ms")
+        return dict(zip(("Z", "cov", "chol", "draws"), ms.tolist()))
+
+    def joint_max_points(self) -> int:
+        n = _i64()
+        self._chk(self.lib.fn("joint_max_points")(self._h, C.byref(n)), "joint_max_points")
+        return n.value
+
     # -- accessors
     def nb_samples(self) -> int:
         n = _i64()
@@ -441,3 +494,13 @@ def device_count(lib) -> int:
     if rc < 0:
         raise EngineError(f"device_count failed: {rc}")
     return n.value
+
+
+def debug_cov_plan(lib, M, N, cus):
+    """gpe_debug_cov_plan: the (tile i, tile j, k0, k1, partial slot) rows of the joint covariance's launch, as an int64 array."""
+    n = lib.fn("debug_cov_plan")(int(M), int(N), int(cus), None, 0)
+    if n < 0:
+        raise EngineError(f"debug_cov_plan: bad arguments ({M}, {N}, {cus})")
+    out = np.zeros((n, 5), dtype=np.int64)
+    lib.fn("debug_cov_plan")(int(M), int(N), int(cus), out.ctypes.data_as(C.POINTER(_i64)), n)
+    return out

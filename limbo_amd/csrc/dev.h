@@ -472,6 +472,19 @@ void launch_small_alpha(hipStream_t s, const SmallAlphaArgs& g, int P);
 void launch_small_add(hipStream_t s, const SmallAddArgs& g, int P, const KParams& kp, const LamParams& lp, const double* x);
 void launch_small_query(hipStream_t s, const SmallQueryArgs& g, const KParams& kp, const LamParams& lp);
 
+// ---- joint posterior over a point batch (joint.hip; include/gpe_joint.h) ------------------------------------------
+// the split of Sigma's product Zt Zt^T (k = N) over workgroups: chunks per tile, and the launch's (tile i, tile j, k0, k1, slot) rows
+int joint_cov_chunks(int64_t M, int64_t N, int cus);
+int joint_cov_plan(int64_t M, int64_t N, int cus, int64_t* out, int64_t cap_rows); // host only
+// Sig (full symmetric, lds) = k(V, V) + jitter I - sum_c Part_c, the partial matrices (ldp, pstride apart) added in ascending c
+void launch_cov_fold(hipStream_t s, const double* Part, int64_t ldp, int64_t pstride, int nch, const double* Qt, int64_t ldq, int64_t M,
+                     const KParams& kp, double jitter, double* Sig, int64_t lds);
+// F[m + M col] = mean_q[m + M p] + kta[m + ldk p] + sum_{j <= m} C[m, j] Z[j + M col], col = s + S p < ncols (mean_q may be null)
+void launch_draws(hipStream_t s, const double* Cm, int64_t ldc, int64_t M, const double* Z, const double* mean_q, const double* kta, int64_t ldk,
+                  int S, int ncols, double* F);
+// out[2 col] = max of column col of F, out[2 col + 1] = the bits of the lowest index (int64) that holds it
+void launch_argmax(hipStream_t s, const double* F, int64_t M, int ncols, double* out);
+
 // ---- micro-benchmarks (microbench.hip) ---------------------------------------------
 double run_mfma_f64_peak(hipStream_t s);
 double run_hbm_stream_peak(hipStream_t s);

@@ -15,6 +15,7 @@
 // every hyper-parameter objective evaluation (kernel_lf_opt.hpp:79); here an evaluation is
 // "same X, new theta" on resident buffers.
 #include "../../include/gpe.h"
+#include "../../include/gpe_joint.h"
 #include "dev.h"
 
 #include <algorithm>
@@ -187,6 +188,8 @@ struct gpe_ctx {
     unsigned long long small_seq = 0;
     bool small_path = true;              // GPE_SMALL=0 disables
     int64_t small_calls = 0;             // calls served by the small path (instrumentation / tests)
+    double joint_ms[4] = {0, 0, 0, 0}; // the last joint call's Z, Sigma, factorisation (host clock) and draws, ms, while profiling is on
+    gpe_ctx* joint = nullptr; // the private scratch context that factors the joint posterior's covariance (joint.hpp): owned, never cloned
     int64_t flow_retries = 0; // sweeps re-run block by block after a hand-off timeout (never expected; see flow_failed)
     bool flow_solve = true; // one data-flow launch for the backward sweep (GPE_FLOW_SOLVE=0: per-block launches)
     bool fuse_panel = true; // k_panel_step instead of the three-launch panel step (GPE_FUSE_PANEL=0 disables)
@@ -670,6 +673,10 @@ int gpe_destroy(gpe_handle c)
         return GPE_ERR_ARG;
     DevGuard g(c);
     hipStreamSynchronize(c->stream);
+    if (c->joint) {
+        gpe_destroy(c->joint);
+        c->joint = nullptr;
+    }
     if (c->gen_ev)
         hipEventDestroy(c->gen_ev);
     if (c->inv_ev) {
@@ -1231,6 +1238,8 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
     return rc;
 }
 
+#include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
+
 int gpe_set_obs_mean(gpe_handle c, const double* obs_mean)
 {
     if (c)
@@ -1451,7 +1460,7 @@ int gpe_flow_retries(gpe_handle c, int64_t* n)
 {
     if (!c || !n)
         return GPE_ERR_ARG;
-    *n = c->flow_retries;
+    *n = c->flow_retries + (c->joint ? c->joint->flow_retries : 0);
     return GPE_OK;
 }
 
@@ -1459,7 +1468,7 @@ int gpe_handover_reruns(gpe_handle c, int64_t* n)
 {
     if (!c || !n)
         return GPE_ERR_ARG;
-    *n = c->handover_reruns;
+    *n = c->handover_reruns + (c->joint ? c->joint->handover_reruns : 0);
     return GPE_OK;
 }
 

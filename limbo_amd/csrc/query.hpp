@@ -12,104 +12,169 @@
 // of the direct-to-LDS matrix-core kernel (gemm.hip, k_gemm_glds), as K^-1's U = L^-T (ensure_inv).  The N x M layout
 // (rounds 1-2, still the path for caller-supplied cross kernels) has the right-hand sides k-contiguous and ran its
 // M N^2 flops through the register-staged kernel: 38 TFLOP/s at N = 16384 against the 53 of the factorisation's updates.
-static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var)
+// The buffers of one chunk of <= mc_max points, carved from gpe_ctx::dQuery, and the launches that fill them — shared by
+// query_transposed (the marginals) and the joint posterior (joint.hpp), which keeps Zt for all its points at once.
+struct QtBufs {
+    int64_t mc_max = 0, ldq = 0, npan = 0, zcols = 0;
+    int nseg = 1, qtile = 128;
+    size_t n_qrm = 0, n_qt = 0, n_kst = 0, n_zt = 0, n_xp = 0, n_part = 0, n_kta = 0, doubles = 0;
+    double *dQrm = nullptr, *dQt = nullptr, *dKst = nullptr, *dZt = nullptr, *dXp = nullptr, *dPart = nullptr, *dKta = nullptr, *dVar = nullptr,
+           *dKvv = nullptr;
+};
+// mc_max: points per chunk (a multiple of 64); zcols >= N: columns of Zt (the joint posterior pads its k range with zero columns)
+static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols)
 {
-    hipStream_t s = c->stream;
-    const int64_t N = c->N, ld = c->ld, nbo = c->nbo;
+    QtBufs b;
+    const int64_t N = c->N, nbo = c->nbo;
     const int D = c->D, P = c->P;
-    // chunk: two ldq x N buffers of <= 2 GiB each
-    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64);
-    mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
-    const int64_t ldq = mc_max + 16; // not a power of two (HBM channel camping on column strides), even, 16-byte rows
-    const int64_t npan = (N + nbo - 1) / nbo;
-    const int nseg = (int)std::max<int64_t>(1, std::min<int64_t>(32, N / 512));
-    const size_t n_qrm = (size_t)(mc_max * std::max(D, 1)), n_qt = (size_t)(ldq * std::max(xt_rows(D), 1));
-    const size_t n_mat = (size_t)(ldq * N), n_xp = (size_t)(npan * nbo * nbo), n_part = (size_t)nseg * std::max(P, 1) * (size_t)ldq;
-    const size_t n_kta = (size_t)(mc_max * P);
-    const size_t need = sizeof(double) * (n_qrm + n_qt + 2 * n_mat + n_xp + n_part + n_kta + 2 * (size_t)mc_max);
-    if (need > c->query_bytes) {
-        if (c->dQuery)
-            hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dQuery, need));
-        c->query_bytes = need;
-    }
-    double* dQrm = c->dQuery;
-    double* dQt = dQrm + n_qrm;
-    double* dKst = dQt + n_qt; // the cross kernel, then the running right-hand side Acc
-    double* dZt = dKst + n_mat;
-    double* dXp = dZt + n_mat;
-    double* dPart = dXp + n_xp;
-    double* dKta = dPart + n_part;
-    double* dVar = dKta + n_kta;
-    double* dKvv = dVar + mc_max;
-    int rc = GPE_OK;
+    b.mc_max = mc_max;
+    b.ldq = mc_max + 16; // not a power of two (HBM channel camping on column strides), even, 16-byte rows
+    b.npan = (N + nbo - 1) / nbo;
+    b.zcols = zcols;
+    b.nseg = (int)std::max<int64_t>(1, std::min<int64_t>(32, N / 512));
+    b.n_qrm = (size_t)(mc_max * std::max(D, 1));
+    b.n_qt = (size_t)(b.ldq * std::max(xt_rows(D), 1));
+    b.n_kst = (size_t)(b.ldq * N);
+    b.n_zt = (size_t)(b.ldq * zcols);
+    b.n_xp = (size_t)(b.npan * nbo * nbo);
+    b.n_part = (size_t)b.nseg * std::max(P, 1) * (size_t)b.ldq;
+    b.n_kta = (size_t)(mc_max * P);
+    b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_xp + b.n_part + b.n_kta + 2 * (size_t)mc_max;
     // The tile of every product below is picked from N alone, never from the batch: the 128 x 128 and the 64 x 64 kernels round
     // differently in the last bit (measured, round 6: a point's variance moved by 1.5e-15 with the size of the batch it was asked
     // in, because launch_gemm_sub picks the tile from the live-tile count = from mc).  A point's answer must not depend on the
     // batch around it (tests/test_gpu_configs.py: the 100 000-point batch of configs[2] bitwise equal to chunks of 4096).
-    const int qtile = N >= 1024 ? 128 : 64;
-    if (var) {
-        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-        launch_inv_panels(s, c->dA, ld, N, (int)nbo, c->dXinv, dXp, 0, nullptr, 0); // X_p of every panel, compact
+    b.qtile = N >= 1024 ? 128 : 64;
+    return b;
+}
+static void qt_carve(QtBufs& b, double* base)
+{
+    b.dQrm = base;
+    b.dQt = b.dQrm + b.n_qrm;
+    b.dKst = b.dQt + b.n_qt; // the cross kernel, then the running right-hand side Acc
+    b.dZt = b.dKst + b.n_kst;
+    b.dXp = b.dZt + b.n_zt;
+    b.dPart = b.dXp + b.n_xp;
+    b.dKta = b.dPart + b.n_part;
+    b.dVar = b.dKta + b.n_kta;
+    b.dKvv = b.dVar + b.mc_max;
+}
+// grow gpe_ctx::dQuery to `bytes` (contents are not kept)
+static int query_reserve(gpe_ctx* c, size_t bytes)
+{
+    if (bytes > c->query_bytes) {
+        if (c->dQuery)
+            hipFree(c->dQuery);
+        c->dQuery = nullptr;
+        c->query_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->dQuery, bytes));
+        c->query_bytes = bytes;
     }
+    return GPE_OK;
+}
+static void query_release(gpe_ctx* c)
+{
+    if (c->query_bytes > ((size_t)64 << 20)) { // a large batch: give the memory back
+        hipFree(c->dQuery);
+        c->dQuery = nullptr;
+        c->query_bytes = 0;
+    }
+}
+// X_p of every panel, compact (in front of the first chunk whose Zt is wanted)
+static void qt_panels(gpe_ctx* c, const QtBufs& b)
+{
+    PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+    launch_inv_panels(c->stream, c->dA, c->ld, c->N, (int)c->nbo, c->dXinv, b.dXp, 0, nullptr, 0);
+}
+// one chunk of mc points (host, row-major): the points, Kst, kta (on the device and, kta != null, to kta[m0 + p M]) and,
+// want_z, Zt = Kst L^-T (Kst is destroyed)
+static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
+                     bool want_z)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, ld = c->ld, nbo = c->nbo, ldq = b.ldq;
+    const int D = c->D, P = c->P;
+    double *dKst = b.dKst, *dZt = b.dZt;
+    hipMemcpyAsync(b.dQrm, Xq_chunk, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
+    launch_transpose_x(s, b.dQrm, mc, D, b.dQt, ldq, 0);
+    project_lambda(c, s, b.dQt, ldq, 0, mc);
+    {
+        // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
+        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+        launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldq); // gp.hpp:626-632
+    }
+    if (want_kta) {
+        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
+        launch_kta_t(s, dKst, ldq, N, mc, c->dAl, ld, P, b.dKta, b.mc_max, b.dPart, ldq, b.nseg); // gp.hpp:615
+        if (kta)
+            for (int p = 0; p < P; ++p)
+                hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc,
+                               hipMemcpyDeviceToHost, s);
+    }
+    if (!want_z)
+        return;
+    for (int64_t o0 = 0; o0 < N; o0 += nbo) { // gp.hpp:620, transposed
+        const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
+        {
+            GemmArgs g{};
+            g.C = dZt + o0 * ldq;
+            g.ldc = ldq;
+            g.A = dKst + o0 * ldq;
+            g.lda = ldq;
+            g.B = b.dXp + (o0 / nbo) * (nbo * nbo);
+            g.ldb = nbo;
+            g.m = mc;
+            g.n = pw;
+            g.k = pw;
+            g.overwrite = 1;
+            g.tile = b.qtile;
+            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+            launch_gemm_sub(s, g);
+        }
+        if (oe < N) {
+            GemmArgs g{};
+            g.tile = b.qtile;
+            g.C = dKst + oe * ldq;
+            g.ldc = ldq;
+            g.A = dZt + o0 * ldq;
+            g.lda = ldq;
+            g.B = c->dA + oe + o0 * ld;
+            g.ldb = ld;
+            g.m = mc;
+            g.n = N - oe;
+            g.k = pw;
+            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+            launch_gemm_sub(s, g);
+        }
+    }
+}
+
+static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N;
+    const int D = c->D;
+    // chunk: two ldq x N buffers of <= 2 GiB each
+    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64);
+    mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
+    QtBufs b = qt_layout(c, mc_max, N);
+    {
+        const int e = query_reserve(c, sizeof(double) * b.doubles);
+        if (e)
+            return e;
+    }
+    qt_carve(b, c->dQuery);
+    int rc = GPE_OK;
+    if (var)
+        qt_panels(c, b);
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        hipMemcpyAsync(dQrm, Xq + m0 * D, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
-        launch_transpose_x(s, dQrm, mc, D, dQt, ldq, 0);
-        project_lambda(c, s, dQt, ldq, 0, mc);
-        {
-            // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
-            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-            launch_build_Ks(s, dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldq); // gp.hpp:626-632
-        }
-        if (kta) {
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
-            launch_kta_t(s, dKst, ldq, N, mc, c->dAl, ld, P, dKta, mc_max, dPart, ldq, nseg); // gp.hpp:615
-            for (int p = 0; p < P; ++p)
-                hipMemcpyAsync(kta + m0 + (int64_t)p * M, dKta + (int64_t)p * mc_max, sizeof(double) * (size_t)mc,
-                               hipMemcpyDeviceToHost, s);
-        }
+        qt_chunk(c, b, Xq + m0 * D, mc, kta != nullptr, kta, m0, M, var != nullptr);
         if (var) {
-            for (int64_t o0 = 0; o0 < N; o0 += nbo) { // gp.hpp:620, transposed
-                const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
-                {
-                    GemmArgs g{};
-                    g.C = dZt + o0 * ldq;
-                    g.ldc = ldq;
-                    g.A = dKst + o0 * ldq;
-                    g.lda = ldq;
-                    g.B = dXp + (o0 / nbo) * (nbo * nbo);
-                    g.ldb = nbo;
-                    g.m = mc;
-                    g.n = pw;
-                    g.k = pw;
-                    g.overwrite = 1;
-                    g.tile = qtile;
-                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
-                    launch_gemm_sub(s, g);
-                }
-                if (oe < N) {
-                    GemmArgs g{};
-                    g.tile = qtile;
-                    g.C = dKst + oe * ldq;
-                    g.ldc = ldq;
-                    g.A = dZt + o0 * ldq;
-                    g.lda = ldq;
-                    g.B = c->dA + oe + o0 * ld;
-                    g.ldb = ld;
-                    g.m = mc;
-                    g.n = N - oe;
-                    g.k = pw;
-                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
-                    launch_gemm_sub(s, g);
-                }
-            }
             PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, dQt, ldq, mc, c->kp, dKvv);
-            launch_row_var_t(s, dZt, ldq, N, mc, dKvv, dVar, dPart, ldq, nseg); // gp.hpp:621
-            hipMemcpyAsync(var + m0, dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+            launch_kvv(s, b.dQt, b.ldq, mc, c->kp, b.dKvv);
+            launch_row_var_t(s, b.dZt, b.ldq, N, mc, b.dKvv, b.dVar, b.dPart, b.ldq, b.nseg); // gp.hpp:621
+            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
         if (hipStreamSynchronize(s) != hipSuccess) {
             c->err = "query_batch: stream sync failed";
@@ -117,11 +182,7 @@ static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
         }
     }
     drain_phases(c);
-    if (c->query_bytes > ((size_t)64 << 20)) { // a large batch: give the memory back
-        hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-    }
+    query_release(c);
     return rc;
 }
 
