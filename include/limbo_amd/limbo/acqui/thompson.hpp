@@ -1,7 +1,8 @@
 // limbo/acqui/thompson.hpp — Thompson sampling over a candidate set: batch proposals from ONE model state.
 // Not in the reference (its acquisition functors score one point from the marginals, src/limbo/acqui/ucb.hpp:77-95); built
 // on the joint posterior of model::GP (query_joint / sample, include/gpe_joint.h): q independent function draws over the
-// candidates, each proposes its own maximiser.  A `boptimizer`-shaped loop evaluates the q proposals, add_sample()s them and
+// candidates, each proposes its own maximiser.  A `boptimizer`-shaped loop evaluates the q proposals, brings them back with
+// ONE model::GP::add_samples() (include/gpe_append.h: a blocked update, one alpha solve) — or add_sample() for each — and
 // asks again.
 #ifndef LIMBO_AMD_ACQUI_THOMPSON_HPP
 #define LIMBO_AMD_ACQUI_THOMPSON_HPP

@@ -61,6 +61,7 @@
 
 #include "../../../gpe.h"
 #include "../../../gpe_joint.h"
+#include "../../../gpe_append.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -227,6 +228,40 @@ namespace limbo {
                 _update_mean_observation();
                 this->_compute_obs_mean();
                 this->_compute_incremental_kernel();
+            }
+
+            /// A batch of samples in one blocked update (include/gpe_append.h): what add_sample() for each of them in order leaves,
+            /// to rounding — the q observations of a batch-acquisition round (acqui/thompson.hpp) go in with ONE mean / obs_mean
+            /// update, one append of q rows to L and one alpha solve.  The shape checks are add_sample's (gp.hpp:126-152).
+            void add_samples(const std::vector<Eigen::VectorXd>& samples, const std::vector<Eigen::VectorXd>& observations)
+            {
+                assert(samples.size() == observations.size());
+                const int64_t q = (int64_t)samples.size();
+                if (q == 0)
+                    return;
+                if (_samples.empty()) {
+                    if (_dim_in != (int)samples[0].size()) {
+                        _dim_in = samples[0].size();
+                        _kernel_function = KernelFunction(_dim_in);
+                    }
+                    if (_dim_out != (int)observations[0].size()) {
+                        _dim_out = observations[0].size();
+                        _mean_function = MeanFunction(_dim_out);
+                    }
+                }
+                for (int64_t i = 0; i < q; ++i) {
+                    assert((int)samples[i].size() == _dim_in);
+                    assert((int)observations[i].size() == _dim_out);
+                }
+                const int64_t n0 = (int64_t)_samples.size();
+                _samples.insert(_samples.end(), samples.begin(), samples.end());
+                _observations.conservativeResize(n0 + q, _dim_out);
+                for (int64_t i = 0; i < q; ++i)
+                    for (int p = 0; p < _dim_out; ++p)
+                        _observations(n0 + i, p) = observations[i](p);
+                _update_mean_observation();
+                this->_compute_obs_mean();
+                this->_compute_incremental_block(n0);
             }
 
             /// gp.hpp:159-167
@@ -1083,6 +1118,58 @@ namespace limbo {
                 }
                 _push_kernel();
                 _status_or(_eng.check(gpe_add_sample(_eng.get(), _samples.back().data(), _dim_in, _obs_mean.data(), _dim_out), "gpe_add_sample"));
+                _L_stale = _alpha_stale = _Kinv_stale = true;
+                _inv_kernel_updated = false; // gp.hpp:602
+            }
+
+            /// gp.hpp:573-603 for the rows n0 .. of _samples at once (add_samples); the cases are _compute_incremental_kernel's
+            void _compute_incremental_block(int64_t n0)
+            {
+                const int64_t n1 = _samples.size();
+                if (_host_mode && _use_host(n1) && n0 >= 1 && (int64_t)_matrixL.rows() == n0) {
+                    // on the host: L moves into the final-size matrix once, the rows follow one by one, then alpha once
+                    Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
+                    for (int64_t j = 0; j < n0; ++j) {
+                        const double* src = _matrixL.data() + j * n0;
+                        double* dst = L2.data() + j * n1;
+                        for (int64_t i = j; i < n0; ++i)
+                            dst[i] = src[i];
+                    }
+                    std::vector<double> kcol((size_t)n1), row((size_t)n1);
+                    int bad = 0;
+                    for (int64_t n = n0; n < n1; ++n) {
+                        for (int64_t i = 0; i < n; ++i)
+                            kcol[(size_t)i] = _kernel_function(_samples[i], _samples[n], i, n);
+                        const double knn = _kernel_function(_samples[n], _samples[n], n, n);
+                        const int b = limbo_amd::host_small::append_row(L2.data(), n, n1, kcol.data(), knn, row.data());
+                        for (int64_t j = 0; j <= n; ++j)
+                            L2.data()[n + j * n1] = row[(size_t)j];
+                        if (b && !bad)
+                            bad = b;
+                    }
+                    _matrixL = std::move(L2);
+                    if (bad)
+                        _status = bad;
+                    _host_alpha();
+                    _L_stale = false;
+                    _Kinv_stale = true;
+                    _inv_kernel_updated = false; // gp.hpp:602
+                    return;
+                }
+                if (_host_mode || _use_host(n1) || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K || !_data_on_device
+                    || n0 == 0) {
+                    // crossing the host / device threshold, a functor-built K, an empty model: the full path decides where
+                    _data_on_device = false;
+                    _compute_full_kernel();
+                    return;
+                }
+                _push_kernel();
+                const int64_t q = n1 - n0;
+                std::vector<double> X((size_t)(q * _dim_in));
+                for (int64_t i = 0; i < q; ++i)
+                    for (int d = 0; d < _dim_in; ++d)
+                        X[(size_t)(i * _dim_in + d)] = _samples[(size_t)(n0 + i)](d);
+                _status_or(_eng.check(gpe_add_samples(_eng.get(), X.data(), q, _dim_in, _obs_mean.data(), _dim_out), "gpe_add_samples"));
                 _L_stale = _alpha_stale = _Kinv_stale = true;
                 _inv_kernel_updated = false; // gp.hpp:602
             }

@@ -72,6 +72,33 @@ namespace limbo {
                 limbo::tools::par::loop(0, _dim_out, [&](size_t i) { _gp_models[i].add_sample(sample, limbo::tools::make_vector(observation(i) - mv(i))); });
             }
 
+            /// A batch of samples: every member GP takes its q targets in one blocked update (model::GP::add_samples).  The mean
+            /// functor is evaluated per new point, after ONE update of the mean observation — for a mean that does not depend on
+            /// the observations this is add_sample() for each of them in order, to rounding.
+            void add_samples(const std::vector<Eigen::VectorXd>& samples, const std::vector<Eigen::VectorXd>& observations)
+            {
+                assert(samples.size() == observations.size());
+                if (samples.empty())
+                    return;
+                if (_gp_models.size() == 0) {
+                    _dim_in = samples[0].size();
+                    _dim_out = observations[0].size();
+                    _mean_function = MeanFunction(_dim_out);
+                    _make_models();
+                }
+                for (size_t j = 0; j < samples.size(); ++j)
+                    assert((int)samples[j].size() == _dim_in && (int)observations[j].size() == _dim_out);
+                _observations.insert(_observations.end(), observations.begin(), observations.end());
+                _update_mean_observation();
+                std::vector<std::vector<Eigen::VectorXd>> obs(_dim_out);
+                for (size_t j = 0; j < samples.size(); ++j) {
+                    Eigen::VectorXd mv = _mean_function(samples[j], *this);
+                    for (int i = 0; i < _dim_out; ++i)
+                        obs[i].push_back(limbo::tools::make_vector(observations[j](i) - mv(i)));
+                }
+                limbo::tools::par::loop(0, _dim_out, [&](size_t i) { _gp_models[i].add_samples(samples, obs[i]); });
+            }
+
             /// (mu, one sigma^2 per output)
             std::tuple<Eigen::VectorXd, Eigen::VectorXd> query(const Eigen::VectorXd& v) const
             {

@@ -106,6 +106,10 @@ def _sig(lib, prefix):
             "joint_max_points": [_vp, C.POINTER(_i64)],
             "joint_phase_ms": [_vp, _dp],
             "debug_cov_plan": [_i64, _i64, C.c_int, C.POINTER(_i64), _i64],
+            # include/gpe_append.h: a batch of samples appended in one blocked update
+            "add_samples": [_vp, _dp, _i64, C.c_int, _dp, C.c_int],
+            "append_max_chunk": [],
+            "debug_append_slices": [_i64, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -271,6 +275,24 @@ class Handle:
         assert om.shape[0] == self.N + 1
         rc = self._chk(self.lib.fn("add_sample")(self._h, _d(x), x.size, _d(om), om.shape[1]), "add_sample")
         self.N += 1
+        return rc
+
+    def add_samples(self, Xnew, obs_mean) -> int:
+        """gpe_add_samples (include/gpe_append.h; HIP library only): q rows of Xnew appended in one blocked update; obs_mean has
+        ALL N + q rows.  Returns the status: 0, or the 1-based first non-positive pivot."""
+        om = np.asarray(obs_mean, dtype=np.float64)
+        if om.ndim == 1:
+            om = om[:, None]
+        om = _c(om, "F")
+        X = _c(Xnew)
+        X = X.reshape(-1, self.D if self.N else (X.shape[-1] if X.ndim > 1 else X.size))
+        q, D = X.shape
+        if self.N == 0:
+            self.D = D
+            self.P = om.shape[1]
+        assert om.shape[0] == self.N + q
+        rc = self._chk(self.lib.fn("add_samples")(self._h, _d(X), q, D, _d(om), om.shape[1]), "add_samples")
+        self.N += q
         return rc
 
     def log_lik(self) -> float:
@@ -494,6 +516,19 @@ def device_count(lib) -> int:
     if rc < 0:
         raise EngineError(f"device_count failed: {rc}")
     return n.value
+
+
+def append_max_chunk(lib) -> int:
+    """gpe_append_max_chunk: rows the device tail of gpe_add_samples factorises at once."""
+    return int(lib.fn("append_max_chunk")())
+
+
+def debug_append_slices(lib, n):
+    """gpe_debug_append_slices: (kslice, nslices, slices_cap, scratch_doubles) of the append tail for a factor of order n."""
+    ks, sd, ns, cap = _i64(), _i64(), C.c_int(), C.c_int()
+    if lib.fn("debug_append_slices")(int(n), C.byref(ks), C.byref(ns), C.byref(cap), C.byref(sd)) != 0:
+        raise EngineError(f"debug_append_slices: bad argument {n}")
+    return ks.value, ns.value, cap.value, sd.value
 
 
 def debug_cov_plan(lib, M, N, cus):

@@ -485,6 +485,18 @@ void launch_draws(hipStream_t s, const double* Cm, int64_t ldc, int64_t M, const
 // out[2 col] = max of column col of F, out[2 col + 1] = the bits of the lowest index (int64) that holds it
 void launch_argmax(hipStream_t s, const double* F, int64_t M, int ncols, double* out);
 
+// ---- blocked append of a sample batch (append.hip; include/gpe_append.h) -------------------------------------------
+int append_max_chunk(); // rows the tail factorises at once
+void append_slices(int64_t n, int64_t* kslice, int* nsl); // the split of the k range (length n) of one chunk's product over workgroups
+int append_slices_cap(int64_t n);          // >= the slice count of every order <= n
+size_t append_scratch_doubles(int64_t n);  // scratch of launch_append_tail for a call whose chunks see orders <= n: (cap + 1) matrices
+// q <= append_max_chunk() new rows of the factor A (order n, ld): A[n + a, k] = Zt[a + k ldq] (k < n) and, at (n, n),
+// C = chol(k(V, V) + diag_add I - Zt Zt^T) with V = the SoA points Qt (ldq).  The k range is split over workgroups and folded in
+// a fixed order; info: first non-positive pivot (n + j + 1), written only if still 0.  The caller refreshes the block inverses.
+// scratch holds slices_cap partial matrices, then S; false (nothing launched) if this order needs more slices than that.
+bool launch_append_tail(hipStream_t s, const double* Zt, const double* Qt, int64_t ldq, int q, int64_t n, const KParams& kp, double* A,
+                        int64_t ld, int* info, double* scratch, int slices_cap);
+
 // ---- micro-benchmarks (microbench.hip) ---------------------------------------------
 double run_mfma_f64_peak(hipStream_t s);
 double run_hbm_stream_peak(hipStream_t s);

@@ -16,6 +16,7 @@
 // "same X, new theta" on resident buffers.
 #include "../../include/gpe.h"
 #include "../../include/gpe_joint.h"
+#include "../../include/gpe_append.h"
 #include "dev.h"
 
 #include <algorithm>
@@ -917,23 +918,22 @@ __global__ void k_knn(const double* __restrict__ kcol, int64_t n, double diag_ad
         out[0] = kcol[n] + diag_add;
 }
 
-int gpe_add_sample(gpe_handle c, const double* x, int D, const double* obs_mean, int P)
+// one sample (the caller holds the handle's mutex): obs_mean's first n + 1 rows, leading dimension ldo (<= 0: n + 1) —
+// gpe_add_sample, and gpe_add_samples (append.hpp) while a batch is better served point by point.  prealloc: the caller has
+// allocated an empty handle's buffers (for its whole batch) just now
+static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* obs_mean, int64_t ldo, int P, bool prealloc)
 {
-    if (c)
-        ++c->epoch;
-    if (!c || !x || !obs_mean || D <= 0 || P <= 0)
-        return GPE_ERR_ARG;
-    DevGuard g(c);
-    std::lock_guard<std::mutex> lk(c->mu);
     if (c->host_K)
         return GPE_ERR_UNSUPPORTED;
     hipStream_t s = c->stream;
     if (c->N == 0) { // gp.hpp:128-137
         if (D > GPE_MAX_THETA - 2)
             return GPE_ERR_ARG;
-        int rc = alloc_dev(c, 256, D, P);
-        if (rc)
-            return rc;
+        if (!prealloc) {
+            int rc = alloc_dev(c, 256, D, P);
+            if (rc)
+                return rc;
+        }
         c->D = D;
         c->P = P;
     }
@@ -954,11 +954,14 @@ int gpe_add_sample(gpe_handle c, const double* x, int D, const double* obs_mean,
     }
     const int64_t n = c->N; // index of the new sample
     const int64_t ld = c->ld;
+    if (ldo <= 0)
+        ldo = n + 1;
     digest_kernel(c);
     if (c->small_path && n >= 1 && n <= small_max_n() && P <= 3 && c->have_L) {
         // one launch, no copies (small.hip): x travels as a kernel argument, obs_mean is read from pinned memory
         double* om_stage = c->hSmall + 256;
-        memcpy(om_stage, obs_mean, sizeof(double) * (size_t)((n + 1) * P));
+        for (int p = 0; p < P; ++p)
+            memcpy(om_stage + (int64_t)p * (n + 1), obs_mean + (int64_t)p * ldo, sizeof(double) * (size_t)(n + 1));
         c->hInfo[0] = c->hInfo[1] = 0;
         SmallAddArgs a{};
         a.A = c->dA;
@@ -997,7 +1000,7 @@ int gpe_add_sample(gpe_handle c, const double* x, int D, const double* obs_mean,
     HIPCHK(c, hipMemcpyAsync(c->dY, x, sizeof(double) * D, hipMemcpyHostToDevice, s));
     launch_transpose_x(s, c->dY, 1, D, c->dXt, ld, n);
     project_lambda(c, s, c->dXt, ld, n, 1);
-    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * ld, obs_mean, sizeof(double) * (n + 1),
+    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * ld, obs_mean, sizeof(double) * ldo,
                                sizeof(double) * (n + 1), P, hipMemcpyHostToDevice, s));
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
     // k(x_i, x_new) for i = 0..n (gp.hpp:583-586), no noise yet
@@ -1029,6 +1032,17 @@ int gpe_add_sample(gpe_handle c, const double* x, int D, const double* obs_mean,
         solve_alpha(c);
         enqueue_loglik_terms(c);
     });
+}
+
+int gpe_add_sample(gpe_handle c, const double* x, int D, const double* obs_mean, int P)
+{
+    if (c)
+        ++c->epoch;
+    if (!c || !x || !obs_mean || D <= 0 || P <= 0)
+        return GPE_ERR_ARG;
+    DevGuard g(c);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return add_sample_locked(c, x, D, obs_mean, 0, P, false);
 }
 
 int gpe_log_lik(gpe_handle c, double* out)
@@ -1239,6 +1253,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 }
 
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
+#include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
 
 int gpe_set_obs_mean(gpe_handle c, const double* obs_mean)
 {

@@ -22,10 +22,11 @@ struct QtBufs {
            *dKvv = nullptr;
 };
 // mc_max: points per chunk (a multiple of 64); zcols >= N: columns of Zt (the joint posterior pads its k range with zero columns)
-static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols)
+// N_ (>= 0): size for that many samples instead of the handle's current count (the blocked append reserves for its last chunk)
+static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols, int64_t N_ = -1)
 {
     QtBufs b;
-    const int64_t N = c->N, nbo = c->nbo;
+    const int64_t N = N_ >= 0 ? N_ : c->N, nbo = c->nbo;
     const int D = c->D, P = c->P;
     b.mc_max = mc_max;
     b.ldq = mc_max + 16; // not a power of two (HBM channel camping on column strides), even, 16-byte rows
