@@ -110,11 +110,31 @@ def _sig(lib, prefix):
             "add_samples": [_vp, _dp, _i64, C.c_int, _dp, C.c_int],
             "append_max_chunk": [],
             "debug_append_slices": [_i64, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)],
+            # include/gpe_sparse.h: the sparse pseudo-input GP
+            "sp_create": [C.c_int, C.POINTER(_vp)],
+            "sp_destroy": [_vp],
+            "sp_set_data": [_vp, _dp, _i64, C.c_int, _dp, C.c_int],
+            "sp_set_pseudo": [_vp, _dp, _i64],
+            "sp_set_hparams": [_vp, _dp, C.c_double, C.c_double, C.c_double],
+            "sp_compute": [_vp],
+            "sp_nlml": [_vp, _dp],
+            "sp_objective": [_vp, _dp, C.c_double, C.c_double, C.c_double, _dp],
+            "sp_predict": [_vp, _dp, _i64, _dp, _dp],
+            "sp_get_L": [_vp, _dp, _i64],
+            "sp_get_Lm": [_vp, _dp, _i64],
+            "sp_get_bet": [_vp, _dp],
+            "sp_get_ep": [_vp, _dp],
+            "sp_set_profiling": [_vp, C.c_int],
+            "sp_phase_ms": [_vp, _dp],
+            "debug_gram_plan": [_i64, _i64, _i64, C.c_int, C.POINTER(_i64), _i64],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
             f.argtypes = args
             f.restype = C.c_int
+        f = getattr(lib, prefix + "sp_last_error")
+        f.argtypes = [_vp]
+        f.restype = C.c_char_p
 
 
 class Lib:
@@ -539,3 +559,121 @@ def debug_cov_plan(lib, M, N, cus):
     out = np.zeros((n, 5), dtype=np.int64)
     lib.fn("debug_cov_plan")(int(M), int(N), int(cus), out.ctypes.data_as(C.POINTER(_i64)), n)
     return out
+
+
+def debug_gram_plan(lib, M, N, chunk=0, cus=256):
+    """gpe_debug_gram_plan: the (tile i, tile j, k0, k1, slot) rows of the sparse GP's weighted Gram, as an int64 array
+    (chunk <= 0: the default chunk for M)."""
+    n = lib.fn("debug_gram_plan")(int(M), int(N), int(chunk), int(cus), None, 0)
+    if n < 0:
+        raise EngineError(f"debug_gram_plan: bad arguments ({M}, {N}, {chunk}, {cus})")
+    out = np.zeros((n, 5), dtype=np.int64)
+    lib.fn("debug_gram_plan")(int(M), int(N), int(chunk), int(cus), out.ctypes.data_as(C.POINTER(_i64)), n)
+    return out
+
+
+class SparseHandle:
+    """One sparse pseudo-input GP (SPGP / FITC) behind include/gpe_sparse.h (HIP library only).  Statuses come back as they are:
+    0, the 1-based first non-positive pivot, or a negative GPE_ERR_* — ``check=True`` raises on the negative ones."""
+
+    def __init__(self, lib: Lib, device: int = 0):
+        self.lib = lib
+        self.N = self.M = self.D = self.P = 0
+        h = _vp()
+        rc = lib.fn("sp_create")(device, C.byref(h))
+        if rc < 0:
+            raise EngineError(f"gpe_sp_create failed: status {rc}")
+        self._h = h
+
+    def _chk(self, rc, what, check=True):
+        if rc < 0 and check:
+            m = self.lib.fn("sp_last_error")(self._h)
+            raise EngineError(f"gpe_sp_{what} failed: status {rc} {m.decode() if m else ''}")
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.fn("sp_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, X, obs_zm, check=True):
+        X = _c(X)
+        y = np.asarray(obs_zm, dtype=np.float64)
+        if y.ndim == 1:
+            y = y[:, None]
+        y = _c(y, "F")
+        rc = self._chk(self.lib.fn("sp_set_data")(self._h, _d(X), X.shape[0], X.shape[1], _d(y), y.shape[1]), "set_data", check)
+        if rc == 0:
+            self.N, self.D = X.shape
+            self.P = y.shape[1]
+        return rc
+
+    def set_pseudo(self, Xb, check=True):
+        Xb = _c(Xb)
+        rc = self._chk(self.lib.fn("sp_set_pseudo")(self._h, _d(Xb), Xb.shape[0]), "set_pseudo", check)
+        if rc == 0:
+            self.M = Xb.shape[0]
+        return rc
+
+    def set_hparams(self, log_b, log_c, log_sig, jitter, check=True):
+        b = _c(log_b)
+        return self._chk(self.lib.fn("sp_set_hparams")(self._h, _d(b), float(log_c), float(log_sig), float(jitter)), "set_hparams", check)
+
+    def compute(self, check=True) -> int:
+        return self._chk(self.lib.fn("sp_compute")(self._h), "compute", check)
+
+    def nlml(self):
+        out = np.zeros(max(self.P, 1))
+        self._chk(self.lib.fn("sp_nlml")(self._h, _d(out)), "nlml")
+        return out
+
+    def objective(self, log_b, log_c, log_sig, jitter):
+        """(status, nlml per output): set_hparams + compute + nlml in one call."""
+        b = _c(log_b)
+        out = np.zeros(max(self.P, 1))
+        rc = self._chk(self.lib.fn("sp_objective")(self._h, _d(b), float(log_c), float(log_sig), float(jitter), _d(out)), "objective")
+        return rc, out
+
+    def predict(self, Xt, want_mu=True, want_s2=True):
+        """(mu (T x P) without the mean functor, s2 (T) without the '+ sig' and without a clamp); either may be None."""
+        Xt = _c(Xt).reshape(-1, self.D)
+        T = Xt.shape[0]
+        mu = np.zeros((T, self.P), order="F") if want_mu else None
+        s2 = np.zeros(T) if want_s2 else None
+        self._chk(self.lib.fn("sp_predict")(self._h, _d(Xt), T, _d(mu) if want_mu else None, _d(s2) if want_s2 else None), "predict")
+        return mu, s2
+
+    def get_L(self):
+        L = np.zeros((self.M, self.M), order="F")
+        self._chk(self.lib.fn("sp_get_L")(self._h, _d(L), self.M), "get_L")
+        return L
+
+    def get_Lm(self):
+        L = np.zeros((self.M, self.M), order="F")
+        self._chk(self.lib.fn("sp_get_Lm")(self._h, _d(L), self.M), "get_Lm")
+        return L
+
+    def get_bet(self):
+        b = np.zeros((self.M, self.P), order="F")
+        self._chk(self.lib.fn("sp_get_bet")(self._h, _d(b)), "get_bet")
+        return b
+
+    def get_ep(self):
+        e = np.zeros(self.N)
+        self._chk(self.lib.fn("sp_get_ep")(self._h, _d(e)), "get_ep")
+        return e
+
+    def set_profiling(self, on: bool):
+        self._chk(self.lib.fn("sp_set_profiling")(self._h, int(on)), "set_profiling")
+
+    def phase_ms(self):
+        """{kmn_v, ep, gram, factor, predict} in ms (set_profiling(True) first)."""
+        ms = np.zeros(5)
+        self._chk(self.lib.fn("sp_phase_ms")(self._h, _d(ms)), "phase_ms")
+        return dict(zip(("kmn_v", "ep", "gram", "factor", "predict"), ms.tolist()))

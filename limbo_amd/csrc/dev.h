@@ -497,6 +497,27 @@ size_t append_scratch_doubles(int64_t n);  // scratch of launch_append_tail for 
 bool launch_append_tail(hipStream_t s, const double* Zt, const double* Qt, int64_t ldq, int q, int64_t n, const KParams& kp, double* A,
                         int64_t ld, int* info, double* scratch, int slices_cap);
 
+// ---- sparse pseudo-input GP (sparse.hip; include/gpe_sparse.h) -----------------------------------------------------
+// V (M pseudo-inputs x a chunk of nc points) in either layout of the batched query: element (n, i) at Z[n sn + i si]
+int64_t sparse_default_chunk(int64_t M);             // columns of V per chunk unless GPE_SPARSE_CHUNK says otherwise
+int sparse_gram_slices(int64_t M, int64_t len, int cus); // slices the k range of a chunk of len columns is cut into
+int64_t sparse_gram_plan(int64_t M, int64_t N, int64_t chunk, int cus, int64_t* out, int64_t cap_rows); // host only: gpe_debug_gram_plan
+// ep[n] = 1 + (c - sum_i Z[n, i]^2) / sig, w[n] = 1 / ep[n]   (spgp.hpp:399)
+void launch_sp_ep(hipStream_t s, const double* Z, int64_t sn, int64_t si, int64_t nc, int64_t M, double c, double sig, double* ep, double* w);
+// R[i + p ldr] += sum_n Z[n, i] w[n] y[n + p ldy]
+void launch_sp_r(hipStream_t s, const double* Z, int64_t sn, int64_t si, int64_t nc, int64_t M, const double* w, const double* y, int64_t ldy,
+                 int P, double* R, int64_t ldr);
+// out[0] = sum log ep, out[1 + p] = sum_n y[n, p]^2 / ep[n]
+void launch_sp_sums(hipStream_t s, const double* ep, int64_t N, const double* y, int64_t ldy, int P, double* out);
+void launch_sp_scale(hipStream_t s, const double* Z, int64_t sn, int64_t si, int64_t nc, int64_t M, const double* w, double* Zw);
+// one workgroup per plan row (device copy of sparse_gram_plan's rows of this chunk; n0 / slot0: the chunk's first column / slot).
+// mode 0: partial tiles into Out + (slot - slot0) pstride; 1: A's tiles = the product; 2: += (one slice per tile only)
+void launch_sp_gram(hipStream_t s, const double* Z, int64_t sn, int64_t si, const double* w, int64_t n0, int64_t M, const int64_t* plan,
+                    int64_t rows, int64_t slot0, double* Out, int64_t ldo, int64_t pstride, int mode);
+void launch_sp_fold(hipStream_t s, const double* Part, int64_t ldp, int64_t pstride, int nsl, int first, int64_t M, double* A, int64_t lda);
+void launch_sp_diag_add(hipStream_t s, double* A, int64_t lda, int64_t M, double v);
+void launch_sp_s2(hipStream_t s, const double* v1, const double* v2, double sig, int64_t T, double* s2);
+
 // ---- micro-benchmarks (microbench.hip) ---------------------------------------------
 double run_mfma_f64_peak(hipStream_t s);
 double run_hbm_stream_peak(hipStream_t s);

@@ -17,6 +17,7 @@
 #include "../../include/gpe.h"
 #include "../../include/gpe_joint.h"
 #include "../../include/gpe_append.h"
+#include "../../include/gpe_sparse.h"
 #include "dev.h"
 
 #include <algorithm>
@@ -1254,6 +1255,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
+#include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)
 
 int gpe_set_obs_mean(gpe_handle c, const double* obs_mean)
 {
