@@ -3,14 +3,19 @@
 //
 // Same class shape and public surface as the reference; the model itself lives on the device behind include/gpe_sparse.h
 // (limbo_amd/csrc/sparse.hpp, sparse.hip): L, V chunk by chunk, ep, the weighted Gram, Lm and bet of :394-406, the likelihood of
-// :491, the predictions of :597-608 — O(N M^2) time, O(N + M^2) memory, N in the 10^5 .. 10^6.
+// :491, its gradient of :500-580 (include/gpe_sparse_grad.h), the predictions of :597-608 — O(N M^2) time, O(N + M^2) memory, N in the 10^5 .. 10^6.
 //
 // What differs, by decision:
 //   - HyperParamsOptimizer defaults to opt::Rprop (the reference: NLOpt L-BFGS, which this tree does not have).
-//   - optimize_hyperparams() initialises as :411-429 (a std::mt19937 instead of random_shuffle / srand(time)) and fits the D + 2
-//     log-parameters b, c, sig with the pseudo-inputs HELD FIXED at their initial random subset.  The gradient is a central
-//     difference of gpe_sp_objective with h = 1e-5 (2 (D + 2) evaluations per step; Rprop reads only its sign).
-//     OUT OF SCOPE: the analytic gradient of :500-580, the pseudo-input positions as parameters, and a host path for small N
+//   - optimize_hyperparams() initialises as :411-429 (a std::mt19937 instead of random_shuffle / srand(time)).  Value and analytic
+//     gradient (:500-580) come from ONE gpe_sp_objective_grad per optimiser step (include/gpe_sparse_grad.h).  By default it fits
+//     the D + 2 log-parameters b, c, sig with the pseudo-inputs HELD FIXED at their initial random subset.  Fitting the
+//     pseudo-inputs is OPT-IN: with `BO_PARAM(bool, optimize_pseudo_inputs, true)` in Params::model_spgp (absent = false) and
+//     pseudo-inputs that are not pinned, the parameter vector is the reference's (M + 1) D + 2 (:415), the pseudo-inputs in front,
+//     packed column-major as HyperParams (:99-100) and the gradient dfw (:568) have them.  The start is written in that same
+//     packing; the reference's :421 writes ROWS of the subset into the column-major vector, which scrambles the coordinates of
+//     its initial pseudo-inputs (each still a mixture of data coordinates, none a data point) — not reproduced.
+//     OUT OF SCOPE: a device-side optimiser loop (the optimiser stays on the host, one call per step) and a host path for small N
 //     (every model, however small, is computed on the device).
 //   - set_pseudo_samples / set_h_params / h_params / nlml (additions) pin a model: with pinned pseudo-inputs AND
 //     hyper-parameters compute / add_sample / recompute do not optimise (the reference always does, :389-392), and predict does
@@ -42,6 +47,7 @@
 #include <limbo/tools/math.hpp>
 
 #include "../../../../gpe_sparse.h"
+#include "../../../../gpe_sparse_grad.h"
 
 namespace limbo {
     namespace defaults {
@@ -68,6 +74,15 @@ namespace limbo_amd {
         template <typename Params>
         struct spgp_device<Params, decltype((void)Params::gpu::device())> {
             static int get() { return Params::gpu::device(); }
+        };
+        // Params::model_spgp::optimize_pseudo_inputs() when the user's Params has one, false otherwise
+        template <typename Params, typename = void>
+        struct spgp_fit_pseudo {
+            static bool get() { return false; }
+        };
+        template <typename Params>
+        struct spgp_fit_pseudo<Params, decltype((void)Params::model_spgp::optimize_pseudo_inputs())> {
+            static bool get() { return Params::model_spgp::optimize_pseudo_inputs(); }
         };
     } // namespace detail
 } // namespace limbo_amd
@@ -443,20 +458,45 @@ namespace limbo {
                     throw std::runtime_error("SPGP: the model could not be computed (non-positive pivot " + std::to_string(_status) + ")");
             }
 
-            /// -nlml at w = [log b, log c, log sig], summed over the outputs; a failed factorisation is the worst value
-            double _objective(const Eigen::VectorXd& w) const
+            /// -nlml, summed over the outputs, at x = [the pseudo-inputs, column-major (only with nx = m dim_in > 0), log b, log c, log sig];
+            /// with grad its gradient, from ONE gpe_sp_objective_grad (one `_likelihood(x, true)` of :446-451).  A failed factorisation is
+            /// the worst value, with a zero gradient.
+            double _objective(const Eigen::VectorXd& x, int nx, Eigen::VectorXd* grad = nullptr) const
             {
-                std::vector<double> lb((size_t)_dim_in), out((size_t)_dim_out);
+                const int m = (int)_pseudo_samples.rows();
+                std::vector<double> lb((size_t)_dim_in), out((size_t)_dim_out), xb((size_t)nx), dxb((size_t)nx), dhp((size_t)_dim_in + 2);
+                for (int j = 0; j < m && nx > 0; ++j)
+                    for (int d = 0; d < _dim_in; ++d)
+                        xb[(size_t)(j * _dim_in + d)] = x(j + d * m);
                 for (int d = 0; d < _dim_in; ++d)
-                    lb[(size_t)d] = w(d);
-                const int rc = gpe_sp_objective(_h, lb.data(), w(_dim_in), w(_dim_in + 1), Params::model_spgp::jitter(), out.data());
+                    lb[(size_t)d] = x(nx + d);
+                const double lc = x(nx + _dim_in), ls = x(nx + _dim_in + 1), jit = Params::model_spgp::jitter();
+                int rc = 0;
+                if (grad)
+                    rc = gpe_sp_objective_grad(_h, nx > 0 ? xb.data() : nullptr, lb.data(), lc, ls, jit, out.data(), nx > 0 ? dxb.data() : nullptr,
+                                               dhp.data());
+                else {
+                    if (nx > 0)
+                        rc = gpe_sp_set_pseudo(_h, xb.data(), m);
+                    if (rc == 0)
+                        rc = gpe_sp_objective(_h, lb.data(), lc, ls, jit, out.data());
+                }
                 _fitted = false;
-                if (rc != 0)
-                    return -std::numeric_limits<double>::max();
+                if (nx > 0)
+                    _pseudo_dirty = true; // (the device holds the last point evaluated, not _pseudo_samples)
                 double s = 0.0;
                 for (double v : out)
                     s += v;
-                return std::isfinite(s) ? -s : -std::numeric_limits<double>::max();
+                const bool ok = rc == 0 && std::isfinite(s);
+                if (grad) {
+                    *grad = Eigen::VectorXd(nx + _dim_in + 2);
+                    for (int j = 0; j < m && nx > 0; ++j)
+                        for (int d = 0; d < _dim_in; ++d)
+                            (*grad)(j + d * m) = ok ? -dxb[(size_t)(j * _dim_in + d)] : 0.0;
+                    for (int d = 0; d < _dim_in + 2; ++d)
+                        (*grad)(nx + d) = ok ? -dhp[(size_t)d] : 0.0;
+                }
+                return ok ? -s : -std::numeric_limits<double>::max();
             }
 
             void _optimize_hyperparams()
@@ -497,32 +537,36 @@ namespace limbo {
                     _optimize_init = false;
                 }
                 _upload();
-                const int dim = _dim_in + 2;
+                // the parameter vector: [log b, log c, log sig], or — Params::model_spgp::optimize_pseudo_inputs(), pseudo-inputs not
+                // pinned — the reference's (m + 1) dim_in + 2 (:415) with the pseudo-inputs in front, column-major
+                const int m = (int)_pseudo_samples.rows();
+                const int nx = (limbo_amd::detail::spgp_fit_pseudo<Params>::get() && !_pseudo_pinned) ? m * _dim_in : 0;
                 auto objective = [&](const Eigen::VectorXd& x, bool g) -> opt::eval_t {
-                    const double f = this->_objective(x);
                     if (!g)
-                        return opt::no_grad(f);
-                    const double h = 1e-5;
-                    Eigen::VectorXd grad(dim), xp = x;
-                    for (int j = 0; j < dim; ++j) {
-                        xp(j) = x(j) + h;
-                        const double fp = this->_objective(xp);
-                        xp(j) = x(j) - h;
-                        const double fm = this->_objective(xp);
-                        xp(j) = x(j);
-                        grad(j) = (fp - fm) / (2.0 * h);
-                    }
+                        return opt::no_grad(this->_objective(x, nx));
+                    Eigen::VectorXd grad;
+                    const double f = this->_objective(x, nx, &grad);
                     return opt::eval_t{f, opt::optional_grad_t(grad)};
                 };
-                const Eigen::VectorXd w0 = h_params();
+                Eigen::VectorXd w0(nx + _dim_in + 2);
+                for (int j = 0; j < m && nx > 0; ++j)
+                    for (int d = 0; d < _dim_in; ++d)
+                        w0(j + d * m) = _pseudo_samples(j, d);
+                for (int d = 0; d < _dim_in; ++d)
+                    w0(nx + d) = _b(d);
+                w0(nx + _dim_in) = _c;
+                w0(nx + _dim_in + 1) = _sig;
                 const Eigen::VectorXd w = _hp_optimize(objective, w0, false);
                 // (an optimiser that returns something worse than where it started is not followed)
-                const Eigen::VectorXd& best = _objective(w) >= _objective(w0) ? w : w0;
+                const Eigen::VectorXd& best = _objective(w, nx) >= _objective(w0, nx) ? w : w0;
+                for (int j = 0; j < m && nx > 0; ++j)
+                    for (int d = 0; d < _dim_in; ++d)
+                        _pseudo_samples(j, d) = best(j + d * m);
                 _b = Eigen::VectorXd(_dim_in);
                 for (int d = 0; d < _dim_in; ++d)
-                    _b(d) = best(d);
-                _c = best(_dim_in);
-                _sig = best(_dim_in + 1);
+                    _b(d) = best(nx + d);
+                _c = best(nx + _dim_in);
+                _sig = best(nx + _dim_in + 1);
                 _optimized = true;
                 _fitted = false;
             }

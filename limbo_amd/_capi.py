@@ -127,6 +127,10 @@ def _sig(lib, prefix):
             "sp_set_profiling": [_vp, C.c_int],
             "sp_phase_ms": [_vp, _dp],
             "debug_gram_plan": [_i64, _i64, _i64, C.c_int, C.POINTER(_i64), _i64],
+            # include/gpe_sparse_grad.h: its analytic gradient
+            "sp_grad": [_vp, _dp, _dp],
+            "sp_objective_grad": [_vp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp],
+            "sp_grad_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -677,3 +681,29 @@ class SparseHandle:
         ms = np.zeros(5)
         self._chk(self.lib.fn("sp_phase_ms")(self._h, _d(ms)), "phase_ms")
         return dict(zip(("kmn_v", "ep", "gram", "factor", "predict"), ms.tolist()))
+
+    def grad(self, want_xb=True, check=True):
+        """(status, d_xb (M x D, as the pseudo-inputs were given) or None, d_hp (D + 2: log b .., log c, log sig)): the gradient of
+        sum_p nlml_p of the model as computed (include/gpe_sparse_grad.h)."""
+        gx = np.zeros((self.M, self.D)) if want_xb else None
+        gh = np.zeros(self.D + 2)
+        rc = self._chk(self.lib.fn("sp_grad")(self._h, _d(gx) if want_xb else None, _d(gh)), "grad", check)
+        return rc, gx, gh
+
+    def objective_grad(self, Xb, log_b, log_c, log_sig, jitter, want_xb=True, check=True):
+        """(status, nlml per output, d_xb or None, d_hp): set_pseudo (Xb, M x D with the handle's M, or None: keep) + set_hparams +
+        compute + nlml + grad in one call.  A status other than 0 leaves the outputs as they were created: NaN."""
+        b = _c(log_b)
+        xb = None if Xb is None else _c(Xb).reshape(self.M, self.D)
+        f = np.full(max(self.P, 1), np.nan)
+        gx = np.full((self.M, self.D), np.nan) if want_xb else None
+        gh = np.full(self.D + 2, np.nan)
+        rc = self._chk(self.lib.fn("sp_objective_grad")(self._h, None if xb is None else _d(xb), _d(b), float(log_c), float(log_sig), float(jitter),
+                                                        _d(f), _d(gx) if want_xb else None, _d(gh)), "objective_grad", check)
+        return rc, f, gx, gh
+
+    def grad_phase_ms(self):
+        """{setup, products, rows, tt, finish} of the last gradient in ms (set_profiling(True) first)."""
+        ms = np.zeros(5)
+        self._chk(self.lib.fn("sp_grad_phase_ms")(self._h, _d(ms)), "grad_phase_ms")
+        return dict(zip(("setup", "products", "rows", "tt", "finish"), ms.tolist()))

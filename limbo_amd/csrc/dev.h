@@ -518,6 +518,31 @@ void launch_sp_fold(hipStream_t s, const double* Part, int64_t ldp, int64_t pstr
 void launch_sp_diag_add(hipStream_t s, double* A, int64_t lda, int64_t M, double v);
 void launch_sp_s2(hipStream_t s, const double* v1, const double* v2, double sig, int64_t T, double* s2);
 
+// ---- the sparse GP's analytic gradient (sparse_grad.hip; include/gpe_sparse_grad.h) ------------------------------------
+// a chunk in the transposed layout: Kt[n + j ldq] = K~_jn, ILVt = V~t Lm^-T, B1t = ILVt Lt^-1, IQt = V~t L^-1
+int64_t sparse_grad_default_chunk(int64_t M);                // points per chunk: four M x chunk buffers are live
+int sparse_grad_row_slices(int64_t M, int64_t len, int cus); // slices of a chunk's points in k_sp_grow
+// b1 = Lti^T bet (Lti lower, order M): b1[j + p ldo]
+void launch_sp_gb1(hipStream_t s, const double* Lti, int64_t ld, int64_t M, const double* bet, int64_t ldb, int P, double* b1, int64_t ldo);
+void launch_sp_grs(hipStream_t s, const double* ep, int64_t nc, double* rs); // rs = 1 / sqrt(ep)
+// per point, from ILVt = (Lm^-1 V~)^T and IQt: big = bigsum, R[n + p ldq] = (y~ - mu) / sig; part[3 workgroup + {0, 1, 2}] = shares of
+// S_sig, S_epc, S_mu
+void launch_sp_gcol(hipStream_t s, const double* ILVt, const double* IQt, int64_t ldq, int64_t nc, int64_t M, const double* bet, int64_t ldbet, int P,
+                    const double* y, int64_t ldy, const double* ep, const double* rs, double c, double sig, double dl, double* big, double* R,
+                    double* part);
+// Vst[n + i ldq] = rs[n] Z[n sn + i si] (V of the chunk in either layout -> scaled, transposed); T = A^T (order M, both ld)
+void launch_sp_gvt(hipStream_t s, const double* Z, int64_t sn, int64_t si, int64_t nc, int64_t M, const double* rs, double* Vst, int64_t ldq);
+void launch_sp_gtrans(hipStream_t s, const double* A, double* T, int64_t ld, int64_t M);
+// Racc[j + col ldp] (=, first) or (+=) sum_n G_jn [1, x^, x^2]_n,col over the chunk, S slices folded in ascending order; Part: S x
+// (2 D + 1) x ldp doubles of scratch; Qt: the chunk's SoA coordinates (ldq)
+void launch_sp_grow(hipStream_t s, const double* Kt, const double* B1t, const double* IQt, int64_t ldq, int64_t nc, int64_t M, const double* b1,
+                    int64_t ldb1, int P, const double* big, const double* R, const double* Qt, const KParams& kp, double sig, int S, double* Part,
+                    int64_t ldp, int first, double* Racc);
+// dxb (M x D row-major), dhp (D + 2) from the M x M matrices (symmetric, ldm), Racc and the nblk per-workgroup scalar shares
+void launch_sp_gfinish(hipStream_t s, const double* Xt, int64_t ldx, const KParams& kp, int64_t M, int P, const double* b1, int64_t ldb1,
+                       const double* IQm, const double* IAm, const double* TT, int64_t ldm, const double* Racc, double sig, double dl,
+                       const double* part, int64_t nblk, double* dxb, double* tb, double* cs, double* dhp);
+
 // ---- micro-benchmarks (microbench.hip) ---------------------------------------------
 double run_mfma_f64_peak(hipStream_t s);
 double run_hbm_stream_peak(hipStream_t s);

@@ -18,6 +18,7 @@
 #include "../../include/gpe_joint.h"
 #include "../../include/gpe_append.h"
 #include "../../include/gpe_sparse.h"
+#include "../../include/gpe_sparse_grad.h"
 #include "dev.h"
 
 #include <algorithm>
@@ -1256,6 +1257,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
 #include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)
+#include "sparse_grad.hpp" // its analytic gradient: one more pass over the chunks (include/gpe_sparse_grad.h)
 
 int gpe_set_obs_mean(gpe_handle c, const double* obs_mean)
 {

@@ -25,6 +25,9 @@ struct gpe_sp_ctx {
     std::vector<double> bet;  // M x P, host copy
     std::vector<double> nlml; // P
     double ms[5] = {0, 0, 0, 0, 0};
+    double* dGrad = nullptr; // the gradient's device block (sparse_grad.hpp)
+    int64_t grad_cap = 0;
+    double gms[5] = {0, 0, 0, 0, 0};
     std::string err;
 };
 
@@ -498,7 +501,7 @@ int gpe_sp_destroy(gpe_sp_handle h)
     SpDevGuard g(h);
     hipStreamSynchronize(h->in->stream);
     hipStreamSynchronize(h->sc->stream);
-    void* ps[] = {h->dX, h->dY, h->dEp, h->dW, h->dPart, h->dBet, h->dXp2, h->dSums, h->dPlan};
+    void* ps[] = {h->dX, h->dY, h->dEp, h->dW, h->dPart, h->dBet, h->dXp2, h->dSums, h->dPlan, h->dGrad};
     for (void* p : ps)
         if (p)
             hipFree(p);
