@@ -222,16 +222,16 @@ int gpe_small_calls(gpe_handle h, int64_t* n);
 int gpe_trace(int on);
 int gpe_trace_dump(const char* path);
 /* Test hook, host only (no device is touched): the dispatch table of a data-flow launch of `nt` tile columns x `nb` row strips
- * (csrc/potrf.hip: tail_order; lag = GPE_TAIL_LAG, pair = GPE_TAIL_PAIR) is built and checked — 1: a permutation of the launch's
+ * (csrc/potrf_tail.hip: tail_order; lag = GPE_TAIL_LAG; pair: must be 0, the form it selected left in round 6) is built and checked — 1: a permutation of the launch's
  * tiles in which every workgroup waits for lower-numbered ones only (what makes the launch deadlock-free), 0: not, -1: bad
  * arguments.  The engine runs the same check before it uses a table. */
 int gpe_debug_tail_order(int nt, int nb, int lag, int pair);
-/* Test hook, host only: how the eight waves of k_tail's chain workgroup split its products (csrc/potrf.hip: syrk40, tri_solve32).
+/* Test hook, host only: how the eight waves of k_tail's chain workgroup split its products (csrc/potrf_tail.hip: syrk40, tri_solve32).
  * units10 = five { row block i of 16, column block j of 4 } pairs: the wave's units of the LOWER triangle of the 64 x 64 diagonal
  * block (40 in all, every one needed exactly once); *cols = the first of the wave's eight columns of a 32-column triangular product
  * (its k loop runs to cols + 8).  0: ok, -1: bad arguments. */
 int gpe_debug_chain_split(int wave, int* units10, int* cols);
-/* Test hook, host only: how the update of a ragged order's last block behind a data-flow launch deals its k range (csrc/potrf.hip:
+/* Test hook, host only: how the update of a ragged order's last block behind a data-flow launch deals its k range (csrc/potrf_tail.hip:
  * launch_ragged_update): returns the number of workgroups (0: the general product runs instead — k < 256 or no room for two
  * 64 x 64 slots in scratch_doubles) and *kc = the k rows of each; -1: bad arguments. */
 int gpe_debug_ragged_split(int64_t k, int64_t scratch_doubles, int* kc);

@@ -187,7 +187,7 @@ struct LamParams {
 // rows D .. D+k-1 of Xt, columns [col0, col0+n):  Xt[(D+j) ld + i] = sum_d A[d + j D] Xt[d ld + i]
 void launch_lambda_rows(hipStream_t s, double* Xt, int64_t ld, int64_t col0, int64_t n, const LamParams& lp);
 
-// ---- Cholesky diagonal block (potrf.hip) --------------------------------------------
+// ---- Cholesky diagonal block (potrf.hip; the panel launches: potrf_panel.hip) --------------------------------------------
 // factor the jb x jb (jb <= 64) diagonal block at A (in place, lower) and write the transposed
 // inverse Xt[k + 64 c] = (L11^-1)[c][k] (64 x 64, identity-padded for jb < 64).  info: first bad
 // pivot (1-based, global index = goff + j + 1), written only if *info == 0.
@@ -204,11 +204,11 @@ typedef unsigned long long gpe_epoch_t; // the value of a hand-over flag word: t
 void launch_panel_step(hipStream_t s, double* A, int64_t lda, int64_t j0, int64_t M, int nt, const double* Xt_cur,
                        double* Xt_next, int do_next, int* info, double* Hs, int64_t dnext, int64_t dfirst, int dinit,
                        double* Dacc, gpe_epoch_t* hflag);
-// all steps of the 256-column outer panel at p0 in one launch (potrf.hip: k_panel256); Xt = inverse of the diagonal block at
+// all steps of the 256-column outer panel at p0 in one launch (potrf_panel.hip: k_panel256); Xt = inverse of the diagonal block at
 // p0 (the next three follow at + 4096 each and are written), dnext / Dacc as above
 void launch_panel256(hipStream_t s, double* A, int64_t lda, int64_t p0, int64_t M, double* Xt, int* info, int64_t dnext,
                      double* Dacc, double* S22, double* S22_next, hipEvent_t stop = nullptr);
-// nt tile columns of a panel of nb row strips in one data-flow launch (potrf.hip: k_tail) — the closing columns of the
+// nt tile columns of a panel of nb row strips in one data-flow launch (potrf_tail.hip: k_tail) — the closing columns of the
 // factorisation (nb = nt [+ 1 for the right-hand-side rows]) or a tall head panel (nb > nt); a buffer = the polled quarters
 // of nt block inverses, then a slot per tile
 #define GPE_TAIL_MAX 8192 // (upper bound of the setting; the default: engine.hip)
@@ -238,8 +238,8 @@ struct FlowGate {
     FlowGate(const FlowGate&) = delete;
     FlowGate& operator=(const FlowGate&) = delete;
 };
-int debug_tail_order(int nt, int nb, int lag, int pair); // potrf.hip (host only)
-void debug_chain_split(int wave, int* units10, int* cols); // potrf.hip (host only): the chain workgroup's work split
+int debug_tail_order(int nt, int nb, int lag, int pair); // potrf_tail.hip (host only)
+void debug_chain_split(int wave, int* units10, int* cols); // potrf_tail.hip (host only): the chain workgroup's work split
 static inline int64_t tail_tiles(int64_t nt, int64_t nb) { return nt * nb - nt * (nt - 1) / 2; }
 static inline int64_t tail_buf_doubles(int64_t nt, int64_t nb) { return nt * 3072 + tail_tiles(nt, nb) * 4096; }
 // gen (optional): the launch generates its tiles of K from the samples (and obs_mean's rows from Om) instead of reading A,
@@ -254,11 +254,11 @@ struct TailGen {
     int P;
     const KParams* kp; // host copy (single launches pass it by value; batched ones read the batch table)
 };
-int ragged_split(int64_t k, int64_t scratch_doubles, int* kc_out); // potrf.hip (host only)
+int ragged_split(int64_t k, int64_t scratch_doubles, int* kc_out); // potrf_tail.hip (host only)
 bool launch_ragged_finish(hipStream_t s, double* C, int64_t ldc, const double* A, int64_t ld, int64_t jb, int64_t P, int64_t k,
-                          double* scratch, int64_t scratch_doubles, double* Xt, int* info, int64_t goff); // potrf.hip: update + factor + solve
+                          double* scratch, int64_t scratch_doubles, double* Xt, int* info, int64_t goff); // potrf_tail.hip: update + factor + solve
 bool launch_ragged_update(hipStream_t s, double* C, int64_t ldc, const double* A, int64_t ld, int64_t m, int64_t n, int64_t k,
-                          double* scratch, int64_t scratch_doubles); // potrf.hip: a ragged order's last block behind k_tail
+                          double* scratch, int64_t scratch_doubles); // potrf_tail.hip: a ragged order's last block behind k_tail
 void launch_tail(hipStream_t s, double* A, int64_t lda, int64_t t0, int64_t t1, int64_t N64, int64_t M, double* Xt_all, int* info,
                  double* buf_cur, double* buf_next, const TailGen* gen = nullptr);
 // S22 / S22_next: the polled hand-over buffers (block inverses + head tiles), 33,792 doubles each, holding the all-ones

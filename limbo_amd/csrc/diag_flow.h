@@ -1,4 +1,4 @@
-// diag_flow.h — the 64 x 64 diagonal block as a data-flow of specialised waves (round 2; included by potrf.hip).
+// diag_flow.h — the 64 x 64 diagonal block as a data-flow of specialised waves (round 2; included through potrf_tile.h).
 //
 // The round-1 kernel (DiagRound, potrf.hip) rotates the "owner" role over four factor waves that all execute one barrier per
 // four columns; its stamps (profiles/r02_diag_rounds.log) show three chains of similar length between consecutive barriers
@@ -37,7 +37,7 @@ struct DiagSync {
 #define XH 34
 #define DIAG_XW_DOUBLES (3 * 32 * XH)
 // X leaves with device-scope (write-through) stores: k_panel256's other workgroups read it DURING the launch, possibly behind
-// another XCD's L2 (potrf.hip); for the launches that hand X to the next launch it makes no difference
+// another XCD's L2 (potrf_panel.hip); for the launches that hand X to the next launch it makes no difference
 #define DIAG_XT_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 // Optional early hand-over of the inverse to ANOTHER workgroup of the same launch (k_panel256's next factoring strip):
@@ -74,7 +74,7 @@ static __device__ __forceinline__ void lds_await(const int* p, int want)
 }
 
 #ifdef DIAG_TIMING
-__device__ long long g_flow_ts[8][20]; // [wave][round]: when the wave finished its round
+static __device__ long long g_flow_ts[8][20]; // [wave][round]: when the wave finished its round (static: a copy per file that includes this)
 #ifdef DIAG_NO_STAMPS
 #define FTS(w, G) do { } while (0)
 #else
@@ -419,7 +419,7 @@ struct FlowX<-1, POFF> {
 // ---- the off-diagonal quarter X21 = -X22 (L21 X11) -------------------------------------------------------------------------
 // Round 1 left it to a kernel of its own after the factorisation (k_xinv_complete) because the panel steps can do with the
 // two diagonal quarters (three small products, six barriers: trsm_tile_half).  With all of X the solve against L11 is ONE
-// product (trsm_tile_full, potrf.hip).  Here: W = L21 X11 by the eighth wave while the second half of the block is still being
+// product (trsm_tile_full, potrf_panel.hip).  Here: W = L21 X11 by the eighth wave while the second half of the block is still being
 // factored, X21 = -X22 W by the four update waves once X22 is complete — 32 matrix-core instructions each, ~1 k cycles behind
 // the inversion wave.  mfma4 layouts as in mm16 / st16 (potrf.hip).
 static __device__ __forceinline__ void flow_w_wave(const double* Ls, DiagSync* sy, double* Xw, int lane, int poff = 0)

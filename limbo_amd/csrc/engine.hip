@@ -156,7 +156,7 @@ struct gpe_ctx {
     double* dQuery = nullptr; // query scratch kept between calls while it is small (single-point queries: no malloc/free)
     size_t query_bytes = 0;
     double* dHead = nullptr; // scratch tiles of the fused panel steps (k_panel_step)
-    bool panel_handover = true; // head tiles of a panel step change hands (potrf.hip); GPE_PANEL_HANDOVER=0: re-derived
+    bool panel_handover = true; // head tiles of a panel step change hands (potrf_panel.hip); GPE_PANEL_HANDOVER=0: re-derived
     bool panel_handover_cfg = true; // what the caller / environment chose: a hand-over timeout switches panel_handover off
     int handover_off_left = 0;      // ... for this many evaluations only, then it is re-armed (one hiccup is not forever)
     int64_t handover_reruns = 0;    // evaluations re-run after a hand-over timeout (gpe_handover_reruns)

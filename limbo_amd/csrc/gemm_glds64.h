@@ -1,4 +1,4 @@
-// gemm_glds64.h — pieces of the fp64 MFMA GEMM shared by gemm.hip and potrf.hip (the fused next-panel update):
+// gemm_glds64.h — pieces of the fp64 MFMA GEMM shared by gemm.hip and potrf_panel.hip (the fused next-panel update):
 // triangular tile enumeration, the lane = row C-tile traffic, and the body of the 64 x 64 direct-to-LDS kernel.
 #pragma once
 #include "dev.h"
@@ -433,8 +433,8 @@ struct WaveTileC {
 // 0,2,1,3 — applied to both operands, the sum over k does not care), which keeps the reads
 // conflict-free.
 // skip00: leave tile (0, 0) alone (the fused next-panel update: that tile is the next diagonal block, which the
-// extra workgroup of the same launch updates and factors — potrf.hip:k_upd_fused)
-// hooks of the body (potrf.hip: the next-panel update that also does the panel's last step): `pre` runs once the tile is
+// extra workgroup of the same launch updates and factors — potrf_panel.hip:k_upd_fused)
+// hooks of the body (potrf_panel.hip: the next-panel update that also does the panel's last step): `pre` runs once the tile is
 // known, before the first operand stage is requested; `post` gets the accumulators after the k loop, before the epilogue
 struct Glds64NoHook {
     __device__ __forceinline__ void pre(int, int, int64_t, int64_t, int, int) const {}

@@ -6,7 +6,7 @@
 // substitution is a chain of tiny dependent products — 8 launches per panel, ~1 ms of launch floor
 // at N = 4096, half of the whole inversion.  This kernel removes the chain: in ONE launch it inverts
 // every diagonal nbo x nbo block of L (all panels at once, they are independent), from the 64 x 64
-// block inverses the factorisation already left behind (potrf.hip:k_diag).  The substitution then
+// block inverses the factorisation already left behind (potrf_panel.hip:k_diag).  The substitution then
 // needs two matrix-core launches per panel: Y_p = X_p Acc_p and the update of the rows below.
 // The engine works on the transposes (U = L^-T, upper triangular): every product is then of the form
 // C -= A B^T with both operands contiguous along their non-k index, which is what the LDS-direct matrix-core

@@ -1,5 +1,5 @@
 // kfun_fast.h — the kernel functors' value from z = sum_d ((x1_d - x2_d) / ell_d)^2 with the branch-free exp(-h) of the
-// kernel-matrix build (kbuild.hip) — shared with the data-flow launches of potrf.hip, which generate their own tiles of K
+// kernel-matrix build (kbuild.hip) — shared with the data-flow launches of potrf_tail.hip, which generate their own tiles of K
 // (round 4: K is never written for the columns those launches factor).  squared_exp_ard.hpp:148-150, exp.hpp:97-102,
 // matern_five_halves.hpp:104-113, matern_three_halves.hpp:101-107.
 #pragma once

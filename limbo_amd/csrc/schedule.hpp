@@ -160,7 +160,7 @@ void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M)
     bool la_pending = false; // a bulk update is (possibly) still running on stream2
     size_t la_last = 0;
     // The last <= tail_max columns (all of them when N <= tail_max) go to ONE launch, a tiled data-flow factorisation
-    // (potrf.hip: k_tail): the panels end at t0.  Its columns are whole 64-blocks: t0 .. N64; a ragged last block (N64 .. N,
+    // (potrf_tail.hip: k_tail): the panels end at t0.  Its columns are whole 64-blocks: t0 .. N64; a ragged last block (N64 .. N,
     // fewer than 64 columns) and the right-hand-side rows ride in it as one more row strip and are finished by the panel code
     // below (one small update, the ragged block).  Round 4: up to tall_max columns in front of t0 are one launch of the same
     // kernel too (e0 .. t0, every row strip below riding along), followed by ONE update of everything behind t0 with
@@ -244,7 +244,7 @@ void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M)
                 g.grow0 = N64;
                 g.gcol0 = N64;
                 PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
-                // ONE tile with k up to 2816: dealt to up to 32 workgroups + an ordered fold (potrf.hip); its scratch is the pair of polled
+                // ONE tile with k up to 2816: dealt to up to 32 workgroups + an ordered fold (potrf_tail.hip); its scratch is the pair of polled
                 // buffers the closing launch has just used — dead until the next launch arms all of them again
                 double* const used = c->dTail + ((c->tail_count - 1) & 1) * c->tail_cap;
                 // ... and factored, inverted and its right-hand-side rows solved by the same two launches where that form serves
@@ -277,7 +277,7 @@ void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M)
         const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + nbo, N) < N && c->fuse_panel && c->fuse_diag
             && c->stop_events && pw == nbo && nbo % NB == 0 && nbo >= 2 * NB && ld % 2 == 0
             && std::min<int64_t>(nbo, N - pe) % NB == 0 && pe != stop0;
-        // the whole panel in one launch (potrf.hip: k_panel256): full 256 columns, head tiles and block inverses handed over
+        // the whole panel in one launch (potrf_panel.hip: k_panel256): full 256 columns, head tiles and block inverses handed over
         // between its workgroups
         const bool p256 = c->panel256 && c->fuse_panel && c->panel_handover && !g_batch.bt && nbo == 4 * NB && pw == nbo && pe <= M;
         // In the first panels of a large factorisation the look-ahead stream is the longer one (N = 4096, panel 1: near + far
@@ -676,7 +676,7 @@ int compute_enqueue(gpe_ctx* c)
     const bool flow_al = c->flow_solve && (c->N + NB - 1) / NB <= 256;
     bool rows_done = false; // obs_mean^T under the matrix + the sweep's sentinel: by the build launch itself where it can
     // Round 4: where the data-flow launches begin decides whether K is built at all.  When the first of them starts at
-    // column 0 it generates its tiles itself (potrf.hip: tail_gen_tile): for N <= 2560 the kernel matrix is never written,
+    // column 0 it generates its tiles itself (potrf_tail.hip: tail_gen_tile): for N <= 2560 the kernel matrix is never written,
     // for the tall launch of N = 4096 only the 2560 x 2560 block behind it is — beside the tall launch, on the second stream.
     c->gen_mode = 0;
     {
@@ -841,7 +841,7 @@ template <class Redo> int compute_finish(gpe_ctx* c, Redo redo)
     HIPCHK(c, hipGetLastError());
     drain_phases(c);
     if (c->hInfo[2] != 0) {
-        // a wave of a panel step gave up waiting for a head tile (potrf.hip) — not a reachable state with workgroups
+        // a wave of a panel step gave up waiting for a head tile (potrf_panel.hip) — not a reachable state with workgroups
         // dispatched in index order; the bounded poll is a backstop, as for the sweeps.  The factor is unusable: run the
         // whole evaluation again, from K on, with every workgroup deriving the head tiles itself.
         c->hInfo[0] = c->hInfo[1] = c->hInfo[2] = 0;

@@ -20,7 +20,7 @@
 #include "gemm_glds64.h"
 
 #define NB 64
-#define S2_PS 80 // stride of the [kk][i] operand tiles in LDS (== 16 mod 32, as potrf.hip's PS)
+#define S2_PS 80 // stride of the [kk][i] operand tiles in LDS (== 16 mod 32, as potrf_tile.h's PS)
 #define S2_MS 65 // stride of M in LDS: Mt[k][c] at k * 65 + c
 
 #ifdef S2_TIMING

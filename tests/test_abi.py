@@ -94,7 +94,7 @@ def test_binding_loads_engine_without_gpu():
 
 
 def test_dispatch_tables_of_the_data_flow_launches_are_deadlock_free():
-    """csrc/potrf.hip: tail_order.  A data-flow launch (k_tail) is deadlock-free because every workgroup waits for
+    """csrc/potrf_tail.hip: tail_order.  A data-flow launch (k_tail) is deadlock-free because every workgroup waits for
     lower-numbered ones only; the order is a TABLE (diagonal workgroups early, tiles below the triangle lagging the chain).
     Built and checked on the host for every launch shape the engine can produce up to 64 tile columns — closing launches
     (nb = nt, nt + 1 with the right-hand-side strip), tall launches (nb up to 65), lags 0..5: a permutation of the tiles and, in the
@@ -122,7 +122,7 @@ def test_dispatch_tables_of_the_data_flow_launches_are_deadlock_free():
 
 
 def test_chain_workgroup_splits_its_products_evenly_and_completely():
-    """csrc/potrf.hip: syrk40 / tri_solve32 (round 5).  The chain workgroup of a data-flow launch multiplies only what is kept: of
+    """csrc/potrf_tail.hip: syrk40 / tri_solve32 (round 5).  The chain workgroup of a data-flow launch multiplies only what is kept: of
     the 64 units of 16 x 4 of a diagonal block's update Y Y^T, the 40 that touch the LOWER triangle — five per wave, every unit once —
     and, against the triangular 32 x 32 block inverses, k ranges that stop at a wave's last column, dealt so that the two waves of a
     SIMD (w and w + 4) add up to the same.  The device code's own mapping functions, called on the host."""
@@ -153,7 +153,7 @@ def test_chain_workgroup_splits_its_products_evenly_and_completely():
 
 
 def test_ragged_block_update_deals_its_k_range_completely():
-    """csrc/potrf.hip: launch_ragged_update (round 5).  The last block of a ragged order is updated over everything the data-flow
+    """csrc/potrf_tail.hip: launch_ragged_update (round 5).  The last block of a ragged order is updated over everything the data-flow
     launch factored (k = 256 .. 2816) by up to 32 workgroups of kc rows each + an ordered fold: the chunks cover [0, k) exactly,
     the last one is not empty, kc is a multiple of the kernel's 32-row blocks, the slots fit the scratch, and small k / small
     scratch fall back to the general product."""

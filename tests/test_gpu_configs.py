@@ -453,7 +453,7 @@ def test_gpu_sweep_retry_path_gives_the_same_results():
 
 
 def test_gpu_panel_head_tiles_handed_over_or_rederived_give_the_same_factor(engine_lib, tmp_path):
-    """A fused panel step gets the L tiles of the panel's head row blocks from the workgroups that own them (potrf.hip:
+    """A fused panel step gets the L tiles of the panel's head row blocks from the workgroups that own them (potrf_panel.hip:
     write-through stores + a flag word per tile); a workgroup that runs out of patience re-derives them from A, which is
     also what GPE_PANEL_HANDOVER=0 selects for every workgroup.  Both orders of arithmetic are the same products, so L
     must agree to the last bit; and it is LAPACK's L to rounding.  N = 1100 covers full panels, a ragged last panel and
@@ -735,7 +735,7 @@ def test_gpu_data_flow_buffers_across_sizes_on_one_handle(engine_lib):
 
 
 def test_gpu_cached_first_look_never_sees_a_stale_slot(engine_lib):
-    """the first look at a polled hand-over slot is a cacheable (workgroup-scope) load (potrf.hip: POLL_CACHED):
+    """the first look at a polled hand-over slot is a cacheable (workgroup-scope) load, only the re-reads are device-scope (potrf_tile.h: PolledTile):
     sound as long as every kernel boundary writes back / invalidates the L2 lines of the slots, so that a word which is not
     the all-ones pattern is this launch's final value — never a leftover of the launch that used the same buffer TWO launches
     ago.  One handle at N = 4096, hyper-parameters cycling through three settings (so the launch two evaluations back

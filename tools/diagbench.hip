@@ -1,6 +1,8 @@
 // diagbench.hip — the 64 x 64 diagonal-block kernel (k_diag) alone: average launch time and the in-kernel round stamps.
 // build: make -C tools diagflow diagbench_0   (the data-flow form / the barrier rounds, -DDIAG_FLOW=0)
 #include "../limbo_amd/csrc/potrf.hip"
+#undef TS // (each file stamps its own array)
+#include "../limbo_amd/csrc/potrf_panel.hip" // k_diag, g_diag_ts
 #include "trace_stub.h"
 #include <vector>
 thread_local BatchLaunch g_batch;

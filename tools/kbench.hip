@@ -139,6 +139,8 @@ int main(int argc, char** argv)
 #ifdef DIAG_TIMING
     extern void dump_diag_timing();
     dump_diag_timing();
+    extern void dump_diag_full_timing();
+    dump_diag_full_timing();
     extern void dump_panel_timing();
     dump_panel_timing();
     { // the four steps of an outer panel one by one (nt = blocks of the panel still to come), full 64-row blocks only
