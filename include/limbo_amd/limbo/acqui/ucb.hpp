@@ -1,15 +1,18 @@
 // limbo/acqui/ucb.hpp — UCB(x) = mu(x) + alpha sqrt(sigma^2(x))   (contract: src/limbo/acqui/ucb.hpp:71-95)
 // plus batch(): the same value for M points through one GP::query_batch — row N1 of SURVEY.md §8f:
 // the acquisition optimiser is the caller that turns per-point query() into the device batch.
+// batch_grad(): value and gradient in the point for M points through one GP::query_grad_batch (include/gpe_query_grad.h).
 // Interface attribution: the template signature / policy shape of this header reproduces, by requirement (drop-in
 // for user code), the public interface of resibots/limbo (Copyright Inria, 2015-; CeCILL-C licence, http://www.cecill.info),
 // file named above.  The implementation behind the interface is this project's own.
 #ifndef LIMBO_ACQUI_UCB_HPP
 #define LIMBO_ACQUI_UCB_HPP
 #include <cmath>
+#include <stdexcept>
 #include <tuple>
 #include <vector>
 #include <Eigen/Core>
+#include <limbo/acqui/afun_gradient.hpp>
 #include <limbo/opt/optimizer.hpp>
 #include <limbo/tools/macros.hpp>
 namespace limbo {
@@ -29,8 +32,8 @@ namespace limbo {
             template <typename AggregatorFunction>
             opt::eval_t operator()(const Eigen::VectorXd& v, const AggregatorFunction& afun, bool gradient) const
             {
-                assert(!gradient);
-                (void)gradient;
+                if (gradient)
+                    return _one_with_gradient(v, afun, limbo_amd::afun_differentiable<AggregatorFunction>());
                 Eigen::VectorXd mu;
                 double sigma;
                 std::tie(mu, sigma) = _model.query(v);
@@ -54,8 +57,55 @@ namespace limbo {
                 return out;
             }
 
+            /// values[m] as batch(), grads[m] = d afun/d mu . dmu + alpha / (2 sigma) grad sigma^2 at points[m]: one device batch.
+            /// d afun / d mu: limbo_amd::afun_gradient (FirstElem, or an aggregator with gradient(mu)).  The mean functor's own
+            /// derivative is not included (GP::query_grad_batch).
+            template <typename AggregatorFunction>
+            void batch_grad(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun, std::vector<double>& values,
+                std::vector<Eigen::VectorXd>& grads) const
+            {
+                Eigen::MatrixXd mu, ds2;
+                Eigen::VectorXd s2;
+                std::vector<Eigen::MatrixXd> dmu;
+                _model.query_grad_batch(points, mu, s2, dmu, ds2);
+                values.resize(points.size());
+                grads.resize(points.size());
+                for (size_t m = 0; m < points.size(); ++m) {
+                    Eigen::VectorXd row(mu.cols());
+                    for (int p = 0; p < (int)mu.cols(); ++p)
+                        row(p) = mu(m, p);
+                    const double sigma = std::sqrt(s2(m));
+                    values[m] = afun(row) + Params::acqui_ucb::alpha() * sigma;
+                    const Eigen::VectorXd da = limbo_amd::afun_gradient(afun, row);
+                    Eigen::VectorXd g(ds2.cols());
+                    for (int d = 0; d < (int)ds2.cols(); ++d) {
+                        double s = 0.0;
+                        for (int p = 0; p < (int)mu.cols(); ++p)
+                            s += da(p) * dmu[m](p, d);
+                        g(d) = s + (sigma > 0 ? Params::acqui_ucb::alpha() / (2.0 * sigma) * ds2(m, d) : 0.0);
+                    }
+                    grads[m] = g;
+                }
+            }
+
         protected:
             const Model& _model;
+
+            // operator() with gradient == true: batch_grad() for one point.  An aggregator without a derivative (limbo_amd::
+            // afun_differentiable) keeps compiling for gradient == false and throws here; batch_grad() itself does not compile.
+            template <typename AggregatorFunction>
+            opt::eval_t _one_with_gradient(const Eigen::VectorXd& v, const AggregatorFunction& afun, std::true_type) const
+            {
+                std::vector<double> val;
+                std::vector<Eigen::VectorXd> gr;
+                batch_grad(std::vector<Eigen::VectorXd>(1, v), afun, val, gr);
+                return opt::eval_t{val[0], opt::eval_t::second_type(gr[0])};
+            }
+            template <typename AggregatorFunction>
+            opt::eval_t _one_with_gradient(const Eigen::VectorXd&, const AggregatorFunction&, std::false_type) const
+            {
+                throw std::logic_error("limbo_amd: acqui::UCB with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
+            }
         };
     } // namespace acqui
 } // namespace limbo

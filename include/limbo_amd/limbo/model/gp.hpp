@@ -54,6 +54,7 @@
 #include <limbo/mean/constant.hpp>
 #include <limbo/mean/data.hpp>
 #include <limbo/model/gp/host_small.hpp>
+#include <limbo/model/gp/query_grad.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -62,6 +63,7 @@
 #include "../../../gpe.h"
 #include "../../../gpe_joint.h"
 #include "../../../gpe_append.h"
+#include "../../../gpe_query_grad.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -325,6 +327,54 @@ namespace limbo {
                     for (int p = 0; p < _dim_out; ++p)
                         mu_out(m, p) = kta[(size_t)(m + M * p)] + mv(p);
                     sigma_sq(m) = _finish_sigma(var[(size_t)m]) + _kernel_function.noise();
+                }
+            }
+
+            /// Addition (include/gpe_query_grad.h): query_batch() together with the posterior's GRADIENT in the point — what a
+            /// gradient optimiser of an acquisition function consumes.  mu and sigma_sq are exactly query_batch()'s (mean functor
+            /// added, clamp, + noise); dmu[m] is dim_out x dim_in, dmu[m](p, d) = d mu_p / d v_d at points[m]; dsigma_sq is
+            /// M x dim_in, its row m zero where _finish_sigma clamped the variance.  The mean functor's OWN derivative is not
+            /// included: exact for mean::NullFunction, mean::Constant and mean::Data, whose value does not depend on the point.
+            /// Runs on the model's home device (the dealing of large query_batch() calls over devices does not apply); no samples:
+            /// zeros; a host-resident model with M n below the batch crossover: on the host from matrixL() and
+            /// limbo_amd::query_grad::dk_dv; kernels without device code: std::logic_error.
+            void query_grad_batch(const std::vector<Eigen::VectorXd>& points, Eigen::MatrixXd& mu_out, Eigen::VectorXd& sigma_sq,
+                std::vector<Eigen::MatrixXd>& dmu, Eigen::MatrixXd& dsigma_sq) const
+            {
+                const int64_t M = points.size(), n = _samples.size();
+                const int D = _dim_in, P = _dim_out;
+                mu_out.resize(M, P);
+                sigma_sq.resize(M);
+                dmu.assign((size_t)M, Eigen::MatrixXd::Zero(P, D));
+                dsigma_sq = Eigen::MatrixXd::Zero(M, D);
+                if (M == 0)
+                    return;
+                if (n == 0) {
+                    query_batch(points, mu_out, sigma_sq);
+                    return;
+                }
+                constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
+                if (kind == limbo_amd::KIND_HOST_K)
+                    throw std::logic_error("limbo_amd: query_grad_batch(): this kernel has no device code, hence no derivative in the query point");
+                std::vector<double> kta((size_t)(M * P)), var((size_t)M), dkta((size_t)(M * D * P)), dvar((size_t)(M * D));
+                if (_host_mode && M * n < (int64_t)limbo_amd::host_batch_crossover())
+                    _host_query_grad(points, kta.data(), var.data(), dkta.data(), dvar.data());
+                else {
+                    const std::vector<double> Xq = _joint_points(points);
+                    _eng.check(gpe_query_batch_grad(_eng.get(), Xq.data(), M, kta.data(), var.data(), dkta.data(), dvar.data()), "gpe_query_batch_grad");
+                }
+                for (int64_t m = 0; m < M; ++m) {
+                    Eigen::VectorXd mv = _mean_function(points[m], *this);
+                    for (int p = 0; p < P; ++p) {
+                        mu_out(m, p) = kta[(size_t)(m + M * p)] + mv(p);
+                        for (int d = 0; d < D; ++d)
+                            dmu[(size_t)m](p, d) = dkta[(size_t)(m + M * (d + (int64_t)D * p))];
+                    }
+                    const double s2 = _finish_sigma(var[(size_t)m]);
+                    sigma_sq(m) = s2 + _kernel_function.noise();
+                    if (s2 != 0)
+                        for (int d = 0; d < D; ++d)
+                            dsigma_sq(m, d) = dvar[(size_t)(m + M * d)];
                 }
             }
 
@@ -1356,6 +1406,46 @@ namespace limbo {
                         if (a != b)
                             cov[b + M * a] = cov[a + M * b];
                     }
+            }
+            // gpe_query_batch_grad's four outputs on the host, from matrixL() and alpha() and the kernel's derivative by (kind, log-theta)
+            void _host_query_grad(const std::vector<Eigen::VectorXd>& pts, double* kta, double* var, double* dkta, double* dvar) const
+            {
+                const int64_t M = pts.size(), n = _samples.size();
+                const int D = _dim_in, P = _dim_out;
+                constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
+                const Eigen::VectorXd hp = _kernel_function.h_params();
+                const int nk = (int)hp.size() - (Params::kernel::optimize_noise() ? 1 : 0);
+                const Eigen::MatrixXd& L = matrixL();
+                const Eigen::MatrixXd& al = alpha();
+                std::vector<double> k((size_t)n), w((size_t)n), dk((size_t)D);
+                for (int64_t m = 0; m < M; ++m) {
+                    assert((int)pts[m].size() == D);
+                    for (int64_t i = 0; i < n; ++i)
+                        k[(size_t)i] = _kernel_function(_samples[i], pts[m]);
+                    for (int p = 0; p < P; ++p) {
+                        double s = 0.0;
+                        for (int64_t i = 0; i < n; ++i)
+                            s += k[(size_t)i] * al.data()[i + n * p];
+                        kta[m + M * p] = s;
+                    }
+                    w = k;
+                    limbo_amd::host_small::solve_lower(L.data(), n, n, w.data(), 1, n);
+                    double zz = 0.0;
+                    for (int64_t i = 0; i < n; ++i)
+                        zz += w[(size_t)i] * w[(size_t)i];
+                    var[m] = _kernel_function(pts[m], pts[m]) - zz;
+                    limbo_amd::host_small::solve_lower_t(L.data(), n, n, w.data(), 1, n); // w = K^-1 k
+                    for (int q = 0; q < D * (P + 1); ++q)
+                        (q < D * P ? dkta[m + M * q] : dvar[m + M * (q - D * P)]) = 0.0;
+                    for (int64_t i = 0; i < n; ++i) {
+                        limbo_amd::query_grad::dk_dv(kind, hp.data(), nk, D, pts[m].data(), _samples[i].data(), dk.data());
+                        for (int d = 0; d < D; ++d) {
+                            for (int p = 0; p < P; ++p)
+                                dkta[m + M * (d + (int64_t)D * p)] += al.data()[i + n * p] * dk[(size_t)d];
+                            dvar[m + M * d] -= 2.0 * w[(size_t)i] * dk[(size_t)d];
+                        }
+                    }
+                }
             }
             // F (M x S x P, may be null), argmax / fmax (S x P, may be null)
             void _draws(const std::vector<Eigen::VectorXd>& pts, const std::vector<double>& Z, int S, double jitter, double* F, int64_t* argmax,

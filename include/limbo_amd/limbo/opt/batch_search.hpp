@@ -53,6 +53,24 @@ namespace limbo {
             const Afun& afun;
             eval_t operator()(const Eigen::VectorXd& x, bool g) const { return acqui(x, afun, g); }
             std::vector<double> batch(const std::vector<Eigen::VectorXd>& pts) const { return acqui.batch(pts, afun); }
+            /// values (and, grad, gradients in the point) of many points at once — the objective form of opt::rprop_lockstep
+            /// (opt/batched_rprop.hpp: has_eval_batch); with grad the acquisition object's batch_grad() answers
+            std::vector<eval_t> eval_batch(const std::vector<Eigen::VectorXd>& xs, bool grad) const
+            {
+                std::vector<eval_t> out;
+                out.reserve(xs.size());
+                if (!grad) {
+                    for (double v : acqui.batch(xs, afun))
+                        out.push_back(no_grad(v));
+                    return out;
+                }
+                std::vector<double> val;
+                std::vector<Eigen::VectorXd> gr;
+                acqui.batch_grad(xs, afun, val, gr);
+                for (size_t i = 0; i < xs.size(); ++i)
+                    out.push_back(eval_t{val[i], eval_t::second_type(gr[i])});
+                return out;
+            }
         };
         template <typename Acqui, typename Afun>
         BatchObjective<Acqui, Afun> make_batch_objective(Acqui& a, const Afun& f) { return BatchObjective<Acqui, Afun>{a, f}; }

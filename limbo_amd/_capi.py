@@ -131,6 +131,9 @@ def _sig(lib, prefix):
             "sp_grad": [_vp, _dp, _dp],
             "sp_objective_grad": [_vp, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp],
             "sp_grad_phase_ms": [_vp, _dp],
+            # include/gpe_query_grad.h: the batched posterior with its gradient in the query point
+            "query_batch_grad": [_vp, _dp, _i64, _dp, _dp, _dp, _dp],
+            "query_grad_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -416,6 +419,29 @@ class Handle:
         n = _i64()
         self._chk(self.lib.fn("joint_max_points")(self._h, C.byref(n)), "joint_max_points")
         return n.value
+
+    # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)
+    def query_batch_grad(self, Xq, want=("kta", "var", "dkta", "dvar")):
+        """(kta (M, P), var (M), dkta (M, D, P), dvar (M, D)), None for what `want` leaves out: dkta[m, d, p] = d(k^T alpha_p)/dv_d,
+        dvar[m, d] = d var / dv_d at point m.  No mean functor, no clamp, no + noise."""
+        Xq = _c(Xq).reshape(-1, self.D)
+        M, D, P = Xq.shape[0], self.D, self.P
+        out = {"kta": np.zeros((M, P), order="F"), "var": np.zeros(M), "dkta": np.zeros((M, D * P), order="F"),
+               "dvar": np.zeros((M, D), order="F")}
+        for k in list(out):
+            if k not in want:
+                out[k] = None
+        ptr = [_d(out[k]) if out[k] is not None else None for k in ("kta", "var", "dkta", "dvar")]
+        self._chk(self.lib.fn("query_batch_grad")(self._h, _d(Xq), M, *ptr), "query_batch_grad")
+        if out["dkta"] is not None:
+            out["dkta"] = out["dkta"].reshape(M, D, P, order="F")
+        return out["kta"], out["var"], out["dkta"], out["dvar"]
+
+    def query_grad_phase_ms(self):
+        """{forward, backward, grad} of the last query_batch_grad call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("query_grad_phase_ms")(self._h, _d(ms)), "query_grad_phase_ms")
+        return dict(zip(("forward", "backward", "grad"), ms.tolist()))
 
     # -- accessors
     def nb_samples(self) -> int:

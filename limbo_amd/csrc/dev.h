@@ -485,6 +485,15 @@ void launch_draws(hipStream_t s, const double* Cm, int64_t ldc, int64_t M, const
 // out[2 col] = max of column col of F, out[2 col + 1] = the bits of the lowest index (int64) that holds it
 void launch_argmax(hipStream_t s, const double* F, int64_t M, int ncols, double* out);
 
+// ---- gradient of the batched posterior in the query point (qgrad.hip; include/gpe_query_grad.h) ------------------------
+size_t query_grad_partial_doubles(int nseg, int ncol, int R, int64_t ldp);
+// columns [cbeg, cbeg + ncol) of { alpha_0 .. alpha_{P-1}, -2 Wt } (Wt = (K^-1 k(X, V))^T, M x N, ldw; null unless column P is among
+// them): out[m + ldo (d + Din c)] = sum_i C_c[m, i] d k(v_m, x_i) / d v_d, c counted from cbeg.  The samples are cut into nseg
+// segments whose partials (part: query_grad_partial_doubles) are added in ascending order — no floating-point atomics.
+void launch_query_grad(hipStream_t s, const double* Qt, int64_t ldq, int64_t M, const double* Xt, int64_t ldx, int64_t N, const double* Wt,
+                       int64_t ldw, const double* Al, int64_t lda, int P, const KParams& kp, const LamParams& lp, int cbeg, int ncol, int nseg,
+                       double* part, int64_t ldp, double* out, int64_t ldo);
+
 // ---- blocked append of a sample batch (append.hip; include/gpe_append.h) -------------------------------------------
 int append_max_chunk(); // rows the tail factorises at once
 void append_slices(int64_t n, int64_t* kslice, int* nsl); // the split of the k range (length n) of one chunk's product over workgroups

@@ -19,6 +19,7 @@
 #include "../../include/gpe_append.h"
 #include "../../include/gpe_sparse.h"
 #include "../../include/gpe_sparse_grad.h"
+#include "../../include/gpe_query_grad.h"
 #include "dev.h"
 
 #include <algorithm>
@@ -192,6 +193,7 @@ struct gpe_ctx {
     bool small_path = true;              // GPE_SMALL=0 disables
     int64_t small_calls = 0;             // calls served by the small path (instrumentation / tests)
     double joint_ms[4] = {0, 0, 0, 0}; // the last joint call's Z, Sigma, factorisation (host clock) and draws, ms, while profiling is on
+    double qgrad_ms[3] = {0, 0, 0}; // the last gpe_query_batch_grad call's forward part, backward solve and gradient kernel, ms, while profiling is on
     gpe_ctx* joint = nullptr; // the private scratch context that factors the joint posterior's covariance (joint.hpp): owned, never cloned
     int64_t flow_retries = 0; // sweeps re-run block by block after a hand-off timeout (never expected; see flow_failed)
     bool flow_solve = true; // one data-flow launch for the backward sweep (GPE_FLOW_SOLVE=0: per-block launches)
@@ -1254,6 +1256,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
     return rc;
 }
 
+#include "qgrad.hpp" // the posterior's gradient in the query point over a point batch (include/gpe_query_grad.h)
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
 #include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)

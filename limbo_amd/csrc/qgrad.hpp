@@ -1,0 +1,289 @@
+// qgrad.hpp — the posterior's gradient in the query point over a point batch (include/gpe_query_grad.h): host side.  Kernels: qgrad.hip.
+// A part of engine.hip's translation unit (included there, once, behind query.hpp, whose chunk helpers it shares).
+#pragma once
+
+// the call's own phases — forward part, backward solve, gradient kernel — for gpe_query_grad_phase_ms: four events per chunk,
+// read after the chunk's stream wait
+struct QgMarks {
+    gpe_ctx* c;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit QgMarks(gpe_ctx* c_) : c(c_) {}
+    void mark(int i)
+    {
+        if (c->prof) {
+            ev[i] = get_event(c);
+            hipEventRecord(ev[i], c->stream);
+        }
+    }
+    void collect() // (the stream has been waited for)
+    {
+        for (int q = 0; q < 3; ++q) {
+            float ms = 0.f;
+            if (ev[q] && ev[q + 1] && hipEventSynchronize(ev[q + 1]) == hipSuccess)
+                hipEventElapsedTime(&ms, ev[q], ev[q + 1]);
+            c->qgrad_ms[q] += ms;
+        }
+        for (hipEvent_t& e : ev) {
+            if (e)
+                c->pool.push_back(e);
+            e = nullptr;
+        }
+    }
+};
+
+// the gradient columns of one chunk: the pass over Wt / alpha, and the results to the caller's arrays
+//   Qt: the chunk's SoA points (ldq), Wt: mc x N (ldw) or null; dPartG / dG: scratch (qg_extra)
+static void qg_columns(gpe_ctx* c, const double* Qt, int64_t ldq, int64_t mc, int64_t mc_max, const double* Wt, int64_t ldw, int nseg,
+                       double* dPartG, double* dG, double* dkta, double* dvar, int64_t m0, int64_t M)
+{
+    hipStream_t s = c->stream;
+    const int D = c->D, P = c->P;
+    const int cbeg = dkta ? 0 : P, ncol = (dvar ? P + 1 : P) - cbeg;
+    {
+        PhaseScope ps(c, GPE_PH_QUERY, (double)c->N * mc * ((double)c->kp.D * (ncol + 1) + 40.0));
+        launch_query_grad(s, Qt, ldq, mc, c->dXt, c->ld, c->N, Wt, ldw, c->dAl, c->ld, P, c->kp, lam_params(c), cbeg, ncol, nseg, dPartG, ldq,
+                          dG, mc_max);
+    }
+    if (dkta)
+        hipMemcpy2DAsync(dkta + m0, sizeof(double) * (size_t)M, dG, sizeof(double) * (size_t)mc_max, sizeof(double) * (size_t)mc, (size_t)D * P,
+                         hipMemcpyDeviceToHost, s);
+    if (dvar)
+        hipMemcpy2DAsync(dvar + m0, sizeof(double) * (size_t)M, dG + (int64_t)mc_max * D * (P - cbeg), sizeof(double) * (size_t)mc_max,
+                         sizeof(double) * (size_t)mc, (size_t)D, hipMemcpyDeviceToHost, s);
+}
+// scratch of qg_columns behind the chunk buffers, in doubles: the partials, then the folded columns
+static void qg_extra(const gpe_ctx* c, int nseg, int64_t ldq, int64_t mc_max, size_t* n_part, size_t* n_g)
+{
+    *n_part = query_grad_partial_doubles(nseg, c->P + 1, c->kp.D, ldq);
+    *n_g = (size_t)mc_max * (size_t)c->D * (size_t)(c->P + 1);
+}
+
+// The transposed layout (query_transposed's loop): Zt = Kst L^-T, var from Zt, then Wt = Zt L^-1 into the buffer Kst occupied.
+static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, ld = c->ld, nbo = c->nbo;
+    const int D = c->D;
+    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64); // (the query's rule)
+    mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
+    QtBufs b = qt_layout(c, mc_max, N);
+    size_t n_partg = 0, n_g = 0;
+    const bool grads = dkta || dvar, want_z = var || dvar;
+    if (grads)
+        qg_extra(c, b.nseg, b.ldq, mc_max, &n_partg, &n_g);
+    {
+        const int e = query_reserve(c, sizeof(double) * (b.doubles + n_partg + n_g));
+        if (e)
+            return e;
+    }
+    qt_carve(b, c->dQuery);
+    double* dPartG = b.dKvv + b.mc_max;
+    double* dG = dPartG + n_partg;
+    int rc = GPE_OK;
+    if (want_z)
+        qt_panels(c, b);
+    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
+        const int64_t mc = std::min<int64_t>(mc_max, M - m0), ldq = b.ldq;
+        QgMarks mk(c);
+        mk.mark(0);
+        qt_chunk(c, b, Xq + m0 * D, mc, kta != nullptr, kta, m0, M, want_z);
+        if (var) { // (before Zt is consumed below)
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
+            launch_kvv(s, b.dQt, ldq, mc, c->kp, b.dKvv);
+            launch_row_var_t(s, b.dZt, ldq, N, mc, b.dKvv, b.dVar, b.dPart, ldq, b.nseg); // gp.hpp:621
+            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+        }
+        mk.mark(1);
+        if (dvar) {
+            // Wt = Zt L^-1, from the last outer panel to the first; Zt is the running right-hand side, Wt goes where Kst was:
+            //   Wt[:, p]        = Acc[:, p] X_p                       X_p = inv(L_pp) (qt_panels), untransposed this time
+            //   Acc[:, 0 .. o0) -= Wt[:, p] L[p, 0 .. o0)
+            // Both products have B with k contiguous: the register-staged matrix-core kernel (the direct-to-LDS one takes
+            // operands contiguous along their non-k index only, gemm.hip: glds_ok).
+            for (int64_t o0 = (b.npan - 1) * nbo; o0 >= 0; o0 -= nbo) {
+                const int64_t pw = std::min<int64_t>(nbo, N - o0);
+                {
+                    GemmArgs g{};
+                    g.C = b.dKst + o0 * ldq;
+                    g.ldc = ldq;
+                    g.A = b.dZt + o0 * ldq;
+                    g.lda = ldq;
+                    g.B = b.dXp + (o0 / nbo) * (nbo * nbo);
+                    g.ldb = nbo;
+                    g.b_kmajor = 1;
+                    g.m = mc;
+                    g.n = pw;
+                    g.k = pw;
+                    g.overwrite = 1;
+                    g.tile = b.qtile;
+                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+                    launch_gemm_sub(s, g);
+                }
+                if (o0 > 0) {
+                    GemmArgs g{};
+                    g.tile = b.qtile;
+                    g.C = b.dZt;
+                    g.ldc = ldq;
+                    g.A = b.dKst + o0 * ldq;
+                    g.lda = ldq;
+                    g.B = c->dA + o0;
+                    g.ldb = ld;
+                    g.b_kmajor = 1;
+                    g.m = mc;
+                    g.n = o0;
+                    g.k = pw;
+                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+                    launch_gemm_sub(s, g);
+                }
+            }
+        }
+        mk.mark(2);
+        if (grads)
+            qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? b.dKst : nullptr, ldq, b.nseg, dPartG, dG, dkta, dvar, m0, M);
+        mk.mark(3);
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            c->err = "query_batch_grad: stream sync failed";
+            rc = GPE_ERR_HIP;
+        }
+        mk.collect();
+    }
+    drain_phases(c);
+    query_release(c);
+    return rc;
+}
+
+// Where the transposed layout does not serve the model: kta and var by the launches of query_impl's blocked N x M path, and
+// Wt = Kst K^-1 in one product (K^-1: ensure_inv, cached on the handle until K changes; a symmetric copy of its lower triangle)
+static int qgrad_by_inverse(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, ld = c->ld;
+    const int D = c->D, P = c->P;
+    if (dvar) {
+        const int e = ensure_inv(c);
+        if (e)
+            return e;
+    }
+    int64_t mc_max = std::max<int64_t>(64, ((int64_t)1 << 28) / std::max<int64_t>(ld, 1)); // (query_impl's rule)
+    mc_max = round_up(std::min<int64_t>(mc_max, round_up(M, 64)), 64);
+    const int64_t ldq = mc_max, ldt = mc_max + 16;
+    const int nseg = qt_layout(c, mc_max, N).nseg, qtile = qt_layout(c, mc_max, N).qtile;
+    const bool grads = dkta || dvar;
+    const size_t n_qrm = (size_t)(mc_max * std::max(D, 1)), n_qt = (size_t)(ldq * std::max(xt_rows(D), 1));
+    const size_t n_ks = (size_t)(ld * mc_max), n_kta = (size_t)(mc_max * P);
+    const size_t n_t = dvar ? (size_t)(ldt * N) : 0, n_ki = dvar ? (size_t)(ld * N) : 0;
+    size_t n_partg = 0, n_g = 0;
+    if (grads)
+        qg_extra(c, nseg, ldt, mc_max, &n_partg, &n_g);
+    {
+        const int e = query_reserve(c, sizeof(double) * (n_qrm + n_qt + n_ks + n_kta + 2 * (size_t)mc_max + 2 * n_t + n_ki + n_partg + n_g));
+        if (e)
+            return e;
+    }
+    double* dQrm = c->dQuery;
+    double* dQt = dQrm + n_qrm;
+    double* dKs = dQt + n_qt;
+    double* dKta = dKs + n_ks;
+    double* dVar = dKta + n_kta;
+    double* dKvv = dVar + mc_max;
+    double* dKst = dKvv + mc_max; // the cross kernel with the points contiguous
+    double* dWt = dKst + n_t;
+    double* dKi = dWt + n_t;
+    double* dPartG = dKi + n_ki;
+    double* dG = dPartG + n_partg;
+    if (dvar) {
+        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+        launch_copy2d(s, c->dKinv, ld, dKi, ld, N, N);
+        launch_symmetrize_from_lower(s, dKi, ld, N);
+    }
+    int rc = GPE_OK;
+    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
+        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
+        QgMarks mk(c);
+        mk.mark(0);
+        hipMemcpyAsync(dQrm, Xq + m0 * D, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
+        launch_transpose_x(s, dQrm, mc, D, dQt, ldq, 0);
+        project_lambda(c, s, dQt, ldq, 0, mc);
+        if (kta || var) {
+            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+            launch_build_Ks(s, c->dXt, ld, N, dQt, ldq, mc, c->kp, dKs, ld); // gp.hpp:626-632
+        }
+        if (kta) {
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
+            launch_kta(s, dKs, ld, N, mc, c->dAl, ld, P, dKta, mc_max); // gp.hpp:615
+            for (int p = 0; p < P; ++p)
+                hipMemcpyAsync(kta + m0 + (int64_t)p * M, dKta + (int64_t)p * mc_max, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+        }
+        if (var) {
+            trsm_left_blocked(c, c->dA, dKs, ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
+            launch_kvv(s, dQt, ldq, mc, c->kp, dKvv);
+            launch_col_var(s, dKs, ld, N, mc, dKvv, dVar); // gp.hpp:621
+            hipMemcpyAsync(var + m0, dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+        }
+        mk.mark(1);
+        if (dvar) {
+            {
+                PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+                launch_build_Ks(s, dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldt); // k is symmetric: the transposed block
+            }
+            GemmArgs g{};
+            g.C = dWt;
+            g.ldc = ldt;
+            g.A = dKst;
+            g.lda = ldt;
+            g.B = dKi;
+            g.ldb = ld;
+            g.m = mc;
+            g.n = N;
+            g.k = N;
+            g.overwrite = 1;
+            g.tile = qtile;
+            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+            launch_gemm_sub(s, g);
+        }
+        mk.mark(2);
+        if (grads)
+            qg_columns(c, dQt, ldq, mc, mc_max, dvar ? dWt : nullptr, ldt, nseg, dPartG, dG, dkta, dvar, m0, M);
+        mk.mark(3);
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            c->err = "query_batch_grad: stream sync failed";
+            rc = GPE_ERR_HIP;
+        }
+        mk.collect();
+    }
+    drain_phases(c);
+    query_release(c);
+    return rc;
+}
+
+int gpe_query_batch_grad(gpe_handle c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
+{
+    if (!c || M < 0 || (M > 0 && !Xq))
+        return GPE_ERR_ARG;
+    if (!c->have_L)
+        return GPE_ERR_STATE;
+    if (c->host_K)
+        return GPE_ERR_UNSUPPORTED;
+    if (M == 0 || (!kta && !var && !dkta && !dvar))
+        return GPE_OK;
+    DevGuard g(c);
+    std::lock_guard<std::mutex> lk(c->mu);
+    digest_kernel(c);
+    for (double& ms : c->qgrad_ms)
+        ms = 0.0;
+    static const bool transposed_ok = !(getenv("GPE_QUERY_T") && atoi(getenv("GPE_QUERY_T")) == 0); // (as query_impl)
+    if (transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo)
+        return qgrad_transposed(c, Xq, M, kta, var, dkta, dvar);
+    return qgrad_by_inverse(c, Xq, M, kta, var, dkta, dvar);
+}
+
+int gpe_query_grad_phase_ms(gpe_handle c, double* ms3)
+{
+    if (!c || !ms3)
+        return GPE_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (int q = 0; q < 3; ++q)
+        ms3[q] = c->qgrad_ms[q];
+    return GPE_OK;
+}
