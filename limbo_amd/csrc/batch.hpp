@@ -207,7 +207,7 @@ static int batch_compute_impl(gpe_handle* hs, int G, int* status, const BatchWan
     if (!hs || G < 0)
         return GPE_ERR_ARG;
     std::vector<int> rc(G, 0);
-    static const bool fused_ok = !(getenv("GPE_BATCH") && atoi(getenv("GPE_BATCH")) == 0);
+    static const bool fused_ok = env_not_zero("GPE_BATCH");
     bool fused = fused_ok && G >= 2;
     for (int g = 0; g < G && fused; ++g) {
         gpe_ctx* c = hs[g];
@@ -231,7 +231,7 @@ static int batch_compute_impl(gpe_handle* hs, int G, int* status, const BatchWan
         int worst = GPE_OK;
         // Sub-batches of <= GPE_BT_MAXG GPs, up to four in flight on their own streams: while one sub-batch is in its
         // panel steps (latency-bound workgroups, one per CU) another one's matrix-core updates fill the chip.
-        static const int nsub_env = getenv("GPE_BATCH_SPLIT") ? atoi(getenv("GPE_BATCH_SPLIT")) : 2;
+        static const int nsub_env = (int)env_int("GPE_BATCH_SPLIT", 2);
         int nsub = std::max(1, std::min(4, nsub_env));
         if (G < 16)
             nsub = 1;

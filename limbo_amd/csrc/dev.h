@@ -4,6 +4,18 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+// ---- environment switches (SWITCHES.md); callers keep the result in a function-local static: read once per process ----
+// an integer switch: its value, or dflt when it is not set
+static inline int64_t env_int(const char* name, int64_t dflt)
+{
+    const char* e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+// an on/off switch: on unless it is set to 0 / dflt when it is not set
+static inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
+static inline bool env_not_zero(const char* name) { return env_flag(name, true); }
 
 #define GPE_MAX_THETA 64
 #define GPE_MAX_P 8 // outputs handled per solve launch
@@ -291,7 +303,7 @@ struct GemmArgs {
     int overwrite; // 0: C -= A*B^T; 1: C = +A*B^T (no read of C); 2: C += A*B^T
     int fold_len;  // set by launch_gemm_sub (tri): live tiles per folded tile-column pair
     int total;     // set by launch_gemm_sub: logical workgroups (glds kernel)
-    int grid_limit; // > 0: at most this many physical workgroups (they loop) — leaves CUs to another stream
+    int grid_limit; // set by no caller of the product; tools/gemm_sk.hip reads it (goes with the next change of the kernels' arguments)
     int tile;      // 0: pick by problem size; 128 / 64 / 32: force the 128x128 / 64x64 / 32x64 tile
     int rhs_rows;  // the LAST rhs_rows of the m rows of C / A are right-hand-side rows (engine.hip): the direct-to-LDS
                    // kernels update them with plain FMAs instead of a tile row (gemm_glds64.h: gemm_rhs_rows); inside those
@@ -402,7 +414,6 @@ void launch_inv_panels(hipStream_t s, const double* L, int64_t ld, int64_t N, in
                        int64_t ldo, double* OutT, int64_t ldt);
 // A[0 : rows, 0 : cols] = 0 (column-major, lda) — a kernel, not hipMemsetAsync: it takes part in batched launches
 void launch_zero2d(hipStream_t s, double* A, int64_t lda, int64_t rows, int64_t cols);
-void launch_zero_upper(hipStream_t s, double* A, int64_t lda, int64_t n);
 void launch_symmetrize_from_lower(hipStream_t s, double* A, int64_t lda, int64_t n);
 void launch_copy2d(hipStream_t s, const double* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols);
 // add_sample tail: L[n,n] = sqrt(knn - ||row||^2)   (gp.hpp:596-597)

@@ -137,13 +137,6 @@ struct gpe_ctx {
     bool stop_events = true;    // next-panel update signals through its own dispatch (hipExtLaunchKernel stop event)
     bool fuse_diag = true;      // next diagonal block factored inside the next-panel update launch (k_upd_fused)
     bool lookahead = true;             // GPE_LOOKAHEAD=0 disables
-    int bulk_wgs = 192;                // physical workgroups of a look-ahead bulk update
-    int near_wgs = 0;                  // workgroups of the "near" part of a look-ahead update (0: unrestricted — it is what the
-                                       // next panel's update waits for; -1: bulk_wgs)
-    int64_t bulk_free_tiles = 0;       // ... unless it has at least this many 128 x 128 tiles.  250 (the
-                                       // first three far updates at N = 4096) while the panels ran step by step; with the
-                                       // one-launch panels (64 CUs for ~55 us) every far update is better off unrestricted:
-                                       // 640 -> 651/s at N = 4096 for 0..100, round 3
     std::mutex mu;
     int64_t N = 0, cap = 0, ld = 0;
     int D = 0, P = 0;
@@ -501,11 +494,8 @@ static LamParams lam_params(const gpe_ctx* c)
 
 #include "inverse.hpp" // K^-1 (the recursion on the factor and the panel form), the LOO weight matrix, the gradient objectives' enqueue
 
-// The look-ahead stream runs the bulk of a trailing update while the main stream factors the next
-// panel.  A GEMM workgroup (147 KB LDS) and a panel-step workgroup (115 KB) cannot share a CU, so a
-// bulk update that owns all 256 CUs would simply delay the panel: the bulk update is launched with
-// `bulk_wgs` < 256 looping workgroups (gemm.hip, GemmArgs::grid_limit), the other CUs stay free for
-// the critical path.  (A CU mask on the stream was tried first and had no effect.)
+// The look-ahead stream runs the bulk of a trailing update while the main stream factors the next panel; every such update is
+// dispatched unrestricted since round 3 (holding CUs back for the panel lost: 640 -> 651/s at N = 4096, profiles/r03_chain_study.md).
 // The main stream is created at the device's HIGHEST priority, the look-ahead stream at the default one: the runtime keeps a
 // pool of hardware queues per priority, so the two can never share a hardware queue.  With both at the default priority the
 // runtime mapped them onto the SAME queue for some creation histories (a third handle alive, sixteen streams created and
@@ -514,7 +504,7 @@ static LamParams lam_params(const gpe_ctx* c)
 // measurable effect on how the chip schedules the two; GPE_STREAM_PRIO=0 restores two default-priority streams.)
 hipError_t create_main_stream(hipStream_t* st)
 {
-    static const bool use = !(getenv("GPE_STREAM_PRIO") && atoi(getenv("GPE_STREAM_PRIO")) == 0);
+    static const bool use = env_not_zero("GPE_STREAM_PRIO");
     int lo = 0, hi = 0;
     if (use && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo)
         return hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi);
@@ -633,18 +623,13 @@ int gpe_create(int device_id, gpe_handle* out)
     c->hScal = (double*)(c->hPinned + 128);
     c->hSmall = c->hScal + 1024;
     memset(c->hPinned, 0, 128);
-    if (const char* f = getenv("GPE_SMALL"))
-        c->small_path = atoi(f) != 0;
+    c->small_path = env_flag("GPE_SMALL", c->small_path);
     c->dInfo = c->hInfo; // mapped pinned memory: same address on the device (unified addressing)
-    if (const char* f = getenv("GPE_PANEL_HANDOVER"))
-        c->panel_handover = atoi(f) != 0;
+    c->panel_handover = env_flag("GPE_PANEL_HANDOVER", c->panel_handover);
     c->panel_handover_cfg = c->panel_handover;
-    if (const char* f = getenv("GPE_FUSE_DIAG"))
-        c->fuse_diag = atoi(f) != 0;
-    if (const char* f = getenv("GPE_PANEL256"))
-        c->panel256 = atoi(f) != 0;
-    if (const char* f = getenv("GPE_EARLY_BULK_TILES"))
-        c->early_bulk = atoll(f);
+    c->fuse_diag = env_flag("GPE_FUSE_DIAG", c->fuse_diag);
+    c->panel256 = env_flag("GPE_PANEL256", c->panel256);
+    c->early_bulk = env_int("GPE_EARLY_BULK_TILES", c->early_bulk);
     if (const char* f = getenv("GPE_TAIL_MAX")) {
         c->tail_max = std::min<int64_t>(std::max<int64_t>(atoll(f), 0), GPE_TAIL_MAX);
         c->tail_single = 0;
@@ -654,14 +639,10 @@ int gpe_create(int device_id, gpe_handle* out)
     c->batch_tail_max = std::min(c->batch_tail_max, c->tail_max);
     if (const char* f = getenv("GPE_BATCH_TAIL_MAX"))
         c->batch_tail_max = std::min<int64_t>(std::max<int64_t>(atoll(f), 0), c->tail_max);
-    if (const char* f = getenv("GPE_STOP_EVENT"))
-        c->stop_events = atoi(f) != 0;
-    if (const char* f = getenv("GPE_LOOKAHEAD"))
-        c->lookahead = atoi(f) != 0;
-    if (const char* f = getenv("GPE_FLOW_SOLVE"))
-        c->flow_solve = atoi(f) != 0;
-    if (const char* f = getenv("GPE_FUSE_PANEL"))
-        c->fuse_panel = atoi(f) != 0;
+    c->stop_events = env_flag("GPE_STOP_EVENT", c->stop_events);
+    c->lookahead = env_flag("GPE_LOOKAHEAD", c->lookahead);
+    c->flow_solve = env_flag("GPE_FLOW_SOLVE", c->flow_solve);
+    c->fuse_panel = env_flag("GPE_FUSE_PANEL", c->fuse_panel);
     const char* e = getenv("GPE_NBO");
     if (e) {
         int v = atoi(e);
@@ -1166,7 +1147,7 @@ int gpe_hp_objective(gpe_handle c, int kind, const double* th, int n_theta, doub
     int rc = gpe_set_kernel(c, kind, th, n_theta, noise); // kernel_lf_opt.hpp:80
     if (rc)
         return rc;
-    static const bool fused_ok = !(getenv("GPE_HP_FUSED") && atoi(getenv("GPE_HP_FUSED")) == 0);
+    static const bool fused_ok = env_not_zero("GPE_HP_FUSED");
     if (want_grad && grad && fused_ok) {
         // Round 5: ONE enqueue for the whole objective — factorisation, alpha, log-lik terms, K^-1, gradient — and one wait.
         // The separate calls below cost a host round trip between the sweep and K^-1 (~20 us of idle chip), and K^-1's
@@ -1533,8 +1514,6 @@ int gpe_clone_to(gpe_handle src, int device_id, gpe_handle* out)
     c->flow_solve = src->flow_solve;
     c->small_path = src->small_path;
     c->lookahead = src->lookahead;
-    c->bulk_wgs = src->bulk_wgs;
-    c->bulk_free_tiles = src->bulk_free_tiles;
     c->host_K = src->host_K;
     if (src->dA) {
         rc = alloc_dev(c, src->cap, src->D, src->P);

@@ -575,15 +575,13 @@ static void launch_glds64(hipStream_t s, const GemmArgs& g0)
         tiles = (int64_t)nsup * fold;
     }
     g.total = (int)tiles;
-    if (g.grid_limit > 0 && tiles > g.grid_limit)
-        tiles = g.grid_limit;
     // Two shapes.  With more tiles than CUs, two workgroups share a CU (BKT 16, 4 stages, 64 KB) and fill each
     // other's bubbles.  With at most one tile per CU — the next-panel update on the critical path of the
     // factorisation — a workgroup is alone with one wave per SIMD and every k-tile pays its two barriers and the
     // LDS read latency in full (in-kernel stamps: 1944 cycles per 16-deep k-tile for 1024 cycles of MFMA work;
     // halving the number of k-tiles with BKT 32 changed nothing: it is the fragment-read latency before every
     // group of 16 MFMAs).  Eight waves on the tile (two per SIMD) cover each other.
-    if ((int64_t)g.total * g_batch.G > 256 || g.grid_limit > 0)
+    if ((int64_t)g.total * g_batch.G > 256)
         launch_k(k_gemm_glds64<16, 4, 2, 4>, k_gemm_glds64<16, 4, 2, 4, true>, dim3((unsigned)tiles), dim3(256), s, g);
     else
         launch_k(k_gemm_glds64<16, 4, 1, 8>, k_gemm_glds64<16, 4, 1, 8, true>, dim3((unsigned)tiles), dim3(512), s, g);
@@ -686,7 +684,7 @@ static void launch_glds128(hipStream_t s, const GemmArgs& g0)
     const int tiles_m = (int)((g.m + TM - 1) / TM), tiles_n = (int)((g.n + TN - 1) / TN);
     int64_t tiles = (int64_t)tiles_m * tiles_n;
     g.tile_map = nullptr;
-    static const bool tri_map = !(getenv("GPE_TRI_MAP") && atoi(getenv("GPE_TRI_MAP")) == 0);
+    static const bool tri_map = env_not_zero("GPE_TRI_MAP");
     int mapped = 0;
     // (not for batched launches: measured slower there — 8 x 2048 6.44 against 6.70 k evaluations/s, 64 x 2048 8.53 against 8.80:
     // the members' small updates are dealt over the chip by gridDim.z, a member's few tiles gain nothing from the order and lose
@@ -709,14 +707,11 @@ static void launch_glds128(hipStream_t s, const GemmArgs& g0)
         tiles = (int64_t)nsup * fold;
     }
     g.total = (int)tiles;
-    if (g.grid_limit > 0 && tiles > g.grid_limit)
-        tiles = g.grid_limit;
     // Two shapes of the same kernel.  BKT 32 / 147 KB of LDS: one workgroup per CU, fewest barriers — best
-    // when there is at most one tile per CU, and the only choice for the look-ahead update (grid_limit:
-    // the free CUs must stay free).  BKT 16 / 74 KB / <= 128 VGPRs: two workgroups per CU, so one tile's
+    // when there is at most one tile per CU.  BKT 16 / 74 KB / <= 128 VGPRs: two workgroups per CU, so one tile's
     // prologue, epilogue and barrier stalls are covered by the other's MFMAs — 11 % faster on the
     // 465-tile update of N = 4096 (94 -> 84 us), 2-4 % slower when tiles <= CUs.
-    const bool two_per_cu = g.grid_limit <= 0 && (int64_t)g.total * g_batch.G > 256;
+    const bool two_per_cu = (int64_t)g.total * g_batch.G > 256;
     // (ONE workgroup of 16 waves per CU — 2 x 8 waves of 64 x 16, or 4 x 4 of 32 x 32: four waves per SIMD from one barrier
     // group — was measured too: a lone 128 x 128 x 256 tile takes 47.9 us against 47.3 with 8 waves, 4 x 4 is 15 % slower.
     // What reaches 97 % of the matrix-core peak in the k loop is two INDEPENDENT barrier groups per CU: profiles/r03_sk_study.md)
@@ -1036,9 +1031,9 @@ void launch_gemm_sub(hipStream_t s, const GemmArgs& g0)
         GemmArgs q = g0;
         q.m = g0.m - g0.rhs_rows;
         q.rhs_rows = 0; // (for the tile counts below)
-        static const int rhs_fma = getenv("GPE_RHS_FMA") ? atoi(getenv("GPE_RHS_FMA")) : 1; // 0: never, 2: always
+        static const int rhs_fma = (int)env_int("GPE_RHS_FMA", 1); // 0: never, 2: always
         bool fma = false;
-        if (rhs_fma && q.m > 0 && !q.overwrite && glds_ok(q) && g_batch.G == 1 && g0.grid_limit <= 0) {
+        if (rhs_fma && q.m > 0 && !q.overwrite && glds_ok(q) && g_batch.G == 1) {
             auto crosses = [&](int T, int64_t round) { return live_tiles(q, T, T) <= round && live_tiles(g0, T, T) > round; };
             fma = rhs_fma == 2 || crosses(128, 256) || (live_tiles(g0, 128, 128) < 200 && (crosses(64, 512) || crosses(64, 256)));
         }

@@ -296,8 +296,8 @@ struct Inv2Plan {
 
 bool inv2_supported(int64_t N)
 {
-    static const int on = getenv("GPE_INV2") ? atoi(getenv("GPE_INV2")) : 1;
-    static const int64_t min_n = getenv("GPE_INV2_MIN_N") ? atoll(getenv("GPE_INV2_MIN_N")) : 1024;
+    static const int on = (int)env_int("GPE_INV2", 1);
+    static const int64_t min_n = env_int("GPE_INV2_MIN_N", 1024);
     return on && N >= min_n;
 }
 int inv2_partials() { return NPART; }

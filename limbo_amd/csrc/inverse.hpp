@@ -105,7 +105,7 @@ int ensure_inv(gpe_ctx* c)
         c->inv_ok = true; // gp.hpp:263
         return GPE_OK;
     }
-    static const bool inv_panels = !(getenv("GPE_INV_PANELS") && atoi(getenv("GPE_INV_PANELS")) == 0);
+    static const bool inv_panels = env_not_zero("GPE_INV_PANELS");
     c->inv_pad_n = -1; // (the forms below write whole tiles of the U buffer)
     if (inv_panels && c->nbo % 128 == 0 && c->nbo <= 256) {
         // Transposed formulation: U = L^-T (upper triangular) is built in dLinv, K^-1 = U U^T.  Every product below
@@ -124,7 +124,7 @@ int ensure_inv(gpe_ctx* c)
         // product the 16 accumulating launches were slower, 761 against 704 us: they re-read C; underneath the chain they
         // are free.)  The X_p now live in a compact side buffer, so the K^-1 buffer's diagonal blocks are free from the start.
         // Batched launches, profiling runs and GPE_INV_OVERLAP=0 keep everything on one stream, product last, as before.
-        static const bool overlap_ok = !(getenv("GPE_INV_OVERLAP") && atoi(getenv("GPE_INV_OVERLAP")) == 0);
+        static const bool overlap_ok = env_not_zero("GPE_INV_OVERLAP");
         const bool overlap = overlap_ok && !g_batch.bt && !c->prof && c->stop_events && npan >= 4;
         if (overlap && (int64_t)c->xp_cap < npan * nbo * nbo) {
             if (c->dXp)

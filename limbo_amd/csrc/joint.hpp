@@ -58,7 +58,7 @@ static int joint_scratch(gpe_ctx* c, int64_t M, gpe_ctx** out)
 // chip un-split and where the fold launch is a second pass over Sigma for nothing.
 static bool joint_use_splitk(int64_t M, int cus)
 {
-    static const int sw = getenv("GPE_JOINT_SPLITK") ? atoi(getenv("GPE_JOINT_SPLITK")) : -1;
+    static const int sw = (int)env_int("GPE_JOINT_SPLITK", -1);
     if (sw >= 0)
         return sw != 0;
     const int64_t nt = (M + 127) / 128;

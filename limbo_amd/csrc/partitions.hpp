@@ -42,7 +42,7 @@ std::atomic<int> g_live[16]; // live handles per physical device (gpe_create / g
 std::atomic<long long> g_xproc_waits{0}; // data-flow scopes that ran under the inter-process lock (gpe_xproc_waits)
 bool gate_on()
 {
-    static const bool on = !(getenv("GPE_FLOW_GATE") && atoi(getenv("GPE_FLOW_GATE")) == 0);
+    static const bool on = env_not_zero("GPE_FLOW_GATE");
     return on;
 }
 GateDev& gate_dev()
@@ -55,7 +55,7 @@ GateDev& gate_dev()
 namespace {
 bool xproc_on()
 {
-    static const bool on = !(getenv("GPE_XPROC_LOCK") && atoi(getenv("GPE_XPROC_LOCK")) == 0);
+    static const bool on = env_not_zero("GPE_XPROC_LOCK");
     return on;
 }
 // is another process holding a byte of the users file?
@@ -236,7 +236,7 @@ void flow_gate_enter(hipStream_t s)
 }
 static bool partitions_on()
 {
-    static const bool on = !(getenv("GPE_FLOW_PARTITIONS") && atoi(getenv("GPE_FLOW_PARTITIONS")) == 0);
+    static const bool on = env_not_zero("GPE_FLOW_PARTITIONS");
     return on && !g_partitions_broken.load(std::memory_order_relaxed);
 }
 // where a workgroup runs: XCD and (shader engine, array, CU) of it
@@ -393,7 +393,7 @@ ChainScope::ChainScope(gpe_ctx* c_, bool engage, bool may_partition) : c(c_), on
         c->stream2 = g.part_aux[part];
         g.part_dirty[part] = true;
         g_masked_chains.fetch_add(1, std::memory_order_relaxed);
-        static const bool fault = getenv("GPE_PARTITION_FAULT") && atoi(getenv("GPE_PARTITION_FAULT")) != 0; // (test hook: claims the other half)
+        static const bool fault = env_flag("GPE_PARTITION_FAULT", false); // (test hook: claims the other half)
         hipLaunchKernelGGL(k_partition_check, dim3(64), dim3(64), 0, P, g.d_owner, fault ? 1 - part : part, g.h_violation);
     }
     else if (g.depth == 1) {

@@ -1197,7 +1197,7 @@ void launch_tail(hipStream_t s, double* A, int64_t lda, int64_t t0, int64_t t1, 
     // measured (profiles/r04_dispatch_order.log, N = 4096): lag 2..4 -> 794-800 evaluations/s against 735 column by column; a
     // just-in-time window W > 0 LOSES (6: 675, 8: 694, 12: 738, 16: 770): a tile dispatched late has its catch-up products still
     // to do when its row's diagonal workgroup asks for it; waiting workgroups are not what limits the closing launch
-    static const int ord_lag = getenv("GPE_TAIL_LAG") ? atoi(getenv("GPE_TAIL_LAG")) : 3;
+    static const int ord_lag = (int)env_int("GPE_TAIL_LAG", 3);
     a.order = tail_order(a.nt, a.nb, g_batch.bt ? 0 : TAIL_DLEAD, ord_lag);
     const int64_t tiles = tail_tiles(a.nt, a.nb);
     if (gen) {

@@ -162,6 +162,6 @@ struct PolledTile {
 // the bound of the polls inside a launch; test hook GPE_HANDOVER_FAULT: negative = nobody publishes, every hand-over "times out" at once
 static inline int flow_spin_limit()
 {
-    static const bool fault = getenv("GPE_HANDOVER_FAULT") && atoi(getenv("GPE_HANDOVER_FAULT")) != 0;
+    static const bool fault = env_flag("GPE_HANDOVER_FAULT", false);
     return fault ? -16 : GPE_FLOW_SPIN_LIMIT;
 }

@@ -272,7 +272,7 @@ int gpe_query_batch_grad(gpe_handle c, const double* Xq, int64_t M, double* kta,
     digest_kernel(c);
     for (double& ms : c->qgrad_ms)
         ms = 0.0;
-    static const bool transposed_ok = !(getenv("GPE_QUERY_T") && atoi(getenv("GPE_QUERY_T")) == 0); // (as query_impl)
+    static const bool transposed_ok = env_not_zero("GPE_QUERY_T"); // (as query_impl)
     if (transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo)
         return qgrad_transposed(c, Xq, M, kta, var, dkta, dvar);
     return qgrad_by_inverse(c, Xq, M, kta, var, dkta, dvar);

@@ -234,20 +234,15 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
     }
     // a handful of points (the per-point calls of an acquisition functor, gp.hpp:159-191): the forward
     // substitution runs as ONE data-flow launch (k_trsv_fwd_flow, <= GPE_MAX_P right-hand sides) instead of a
-    // blocked matrix solve, whose dependent matrix-core launches are all launch floor there
-    static const bool sweep_ok0 = !(getenv("GPE_QUERY_SWEEP") && atoi(getenv("GPE_QUERY_SWEEP")) == 0);
-    static const bool transposed_ok = !(getenv("GPE_QUERY_T") && atoi(getenv("GPE_QUERY_T")) == 0);
-    const bool few0 = sweep_ok0 && c->flow_solve && M <= GPE_MAX_P && (N + NB - 1) / NB <= 256;
-    if (Xq && !few0 && transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && N >= c->nbo)
+    // blocked matrix solve, whose ~2 N/64 dependent matrix-core launches are all launch floor there
+    static const bool sweep_ok = env_not_zero("GPE_QUERY_SWEEP");
+    static const bool transposed_ok = env_not_zero("GPE_QUERY_T");
+    const bool few = sweep_ok && c->flow_solve && M <= GPE_MAX_P && (N + NB - 1) / NB <= 256;
+    if (Xq && !few && transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && N >= c->nbo)
         return query_transposed(c, Xq, M, kta, var);
     // chunk so that the N x mc cross matrix stays under ~2 GiB
     int64_t mc_max = std::max<int64_t>(64, ((int64_t)1 << 28) / std::max<int64_t>(ld, 1));
     mc_max = round_up(std::min<int64_t>(mc_max, round_up(M, 64)), 64);
-    // a handful of points (the per-point calls of an acquisition functor, gp.hpp:159-191): the forward
-    // substitution runs as ONE data-flow launch (k_trsv_fwd_flow, <= GPE_MAX_P right-hand sides) instead of the
-    // blocked matrix solve, whose ~2 N/64 dependent matrix-core launches are all launch floor here
-    static const bool sweep_ok = !(getenv("GPE_QUERY_SWEEP") && atoi(getenv("GPE_QUERY_SWEEP")) == 0);
-    const bool few = sweep_ok && c->flow_solve && M <= GPE_MAX_P && (N + NB - 1) / NB <= 256;
     if (few)
         mc_max = GPE_MAX_P;
     const int64_t ldq = mc_max;

@@ -27,7 +27,7 @@ static TailPlan tail_plan(const gpe_ctx* c, int64_t N, int64_t M)
     // members' tiles together stay within ~18 rounds of the chip: every member has 256 / G resident workgroups, and a tile
     // holds its CU from dispatch to its last store, mostly waiting — measured (profiles/r04_dispatch_order.log): 8 x N = 2048
     // 1.45 ms per batch against 1.59 through the step-by-step panels, but 64 x 2048 9.0 against 7.0 and 10 x 4096 7.9 against 7.6
-    static const int64_t batch_tiles = getenv("GPE_BATCH_TAIL_TILES") ? atoll(getenv("GPE_BATCH_TAIL_TILES")) : 4608;
+    static const int64_t batch_tiles = env_int("GPE_BATCH_TAIL_TILES", 4608);
     int64_t tmax = g_batch.bt ? c->batch_tail_max : c->tail_max;
     if (!g_batch.bt && tmax >= 2 * NB && pl.N64 <= c->tail_single)
         tmax = std::max(tmax, pl.N64);
@@ -151,346 +151,310 @@ static bool prepare_tail(gpe_ctx* c, const TailPlan& pl, hipStream_t s, const gp
     return true;
 }
 
-void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M)
+// C[rlo:M, c0:c1] -= L[rlo:M, k0:k1] L[c0:c1, k0:k1]^T, the elements on / below the diagonal: every update of the factorisation.
+// Call sites add what differs (rhs_rows, stop_event).
+static GemmArgs tri_update(double* A, int64_t ld, int64_t M, int64_t rlo, int64_t c0, int64_t c1, int64_t k0, int64_t k1)
+{
+    GemmArgs g{};
+    g.C = A + rlo + c0 * ld;
+    g.ldc = ld;
+    g.A = A + rlo + k0 * ld;
+    g.lda = ld;
+    g.B = A + c0 + k0 * ld;
+    g.ldb = ld;
+    g.m = M - rlo;
+    g.n = c1 - c0;
+    g.k = k1 - k0;
+    g.tri = 1;
+    g.grow0 = rlo;
+    g.gcol0 = c0;
+    return g;
+}
+
+// What one stage of the factorisation leaves for the next.
+struct PotrfCarry {
+    bool next_diag_done = false; // the fused next-panel update factored the first diagonal block of the coming panel
+    bool la_pending = false;     // a bulk update is (possibly) still running on stream2 ...
+    size_t la_last = 0;          // ... and la_events[la_last] completes behind it
+    void join(gpe_ctx* c, hipStream_t s)
+    {
+        if (la_pending)
+            hipStreamWaitEvent(s, c->la_events[la_last], 0);
+        la_pending = false;
+    }
+};
+
+// event i of the vector (untimed), created on first use
+static hipEvent_t nth_event(std::vector<hipEvent_t>& evs, size_t i)
+{
+    while (evs.size() <= i) {
+        hipEvent_t e;
+        hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        evs.push_back(e);
+    }
+    return evs[i];
+}
+
+// One outer panel, columns [p0, p0 + nbo) (fewer at the end): factored, then its trailing update.  stop0: where the panels
+// end in front of a data-flow launch (< 0: nowhere) — the panel in front of it updates everything left in one piece.
+static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0, int64_t stop0, PotrfCarry& cy)
 {
     hipStream_t s = c->stream;
     const int64_t ld = c->ld;
     const int64_t nbo = c->nbo;
-    bool next_diag_done = false; // the fused next-panel update factored the first diagonal block of the coming panel
-    bool la_pending = false; // a bulk update is (possibly) still running on stream2
-    size_t la_last = 0;
-    // The last <= tail_max columns (all of them when N <= tail_max) go to ONE launch, a tiled data-flow factorisation
-    // (potrf_tail.hip: k_tail): the panels end at t0.  Its columns are whole 64-blocks: t0 .. N64; a ragged last block (N64 .. N,
-    // fewer than 64 columns) and the right-hand-side rows ride in it as one more row strip and are finished by the panel code
-    // below (one small update, the ragged block).  Round 4: up to tall_max columns in front of t0 are one launch of the same
-    // kernel too (e0 .. t0, every row strip below riding along), followed by ONE update of everything behind t0 with
-    // k = t0 - e0; 256-column panels with look-ahead only in front of e0 (none at N = 4096: three launches factor the matrix).
-    TailPlan pl = tail_plan(c, N, M);
-    if (pl.t0 >= 0 && !g_batch.bt && !prepare_tail(c, pl, s)) // (a batched launch: batch_enqueue_fused prepared every member)
-        pl = TailPlan{};
-    // gen_mode (compute_enqueue): the first data-flow launch generates its tiles of K itself — nobody built them
-    TailGen gen{c->dXt, ld, N, c->dOm, ld, (c->flow_solve && (N + NB - 1) / NB <= 256) ? c->dAl : nullptr, ld, c->P, &c->kp};
-    const int64_t t0 = pl.t0, e0 = pl.e0, N64 = pl.N64;
-    const int64_t stop0 = e0 >= 0 ? e0 : t0; // where the panels end: the panel in front of it updates everything left in one piece
-    for (int64_t p0 = 0; p0 < N; p0 += nbo) {
-        if (e0 >= 0 && p0 == e0) {
-            if (la_pending) {
-                hipStreamWaitEvent(s, c->la_events[la_last], 0);
-                la_pending = false;
-            }
-            {
-                const double w = (double)(t0 - e0), h = (double)(M - e0);
-                PhaseScope ps(c, GPE_PH_POTRF_TALL, w * w * w / 3.0 + (h - w) * w * w);
-                double* pair = c->dTail + 2 * c->tail_cap;
-                launch_tail(s, A, ld, e0, t0, N64, M, c->dXinv, c->dInfo, pair + (c->tall_count & 1) * c->tall_cap,
-                            pair + ((c->tall_count + 1) & 1) * c->tall_cap, c->gen_mode == 2 ? &gen : nullptr);
-                if (c->gen_mode == 2 && c->gen_ev) // the rest of K, built on the second stream beside this launch
-                    hipStreamWaitEvent(s, c->gen_ev, 0);
-                ++c->tall_count;
-                c->tall_lay = pl.nt_tall * 65536 + pl.nb_tall;
-            }
-            { // everything behind t0 -= L[t0:M, e0:t0] L[t0:N, e0:t0]^T: one launch, k = t0 - e0
-                GemmArgs g{};
-                g.C = A + t0 + t0 * ld;
-                g.ldc = ld;
-                g.A = A + t0 + e0 * ld;
-                g.lda = ld;
-                g.B = A + t0 + e0 * ld;
-                g.ldb = ld;
-                // (A ragged order: the columns of its last block, N64 .. N, stay out of this launch — they would be a 23rd column of
-                // 128 x 128 tiles at N = 4100, a second round of the chip, 214 -> 337 us — and take the tall launch's columns together
-                // with the closing launch's in their own update below.  The rows under N64 — the ragged rows and the right-hand sides —
-                // are the launch's "right-hand-side rows": plain FMAs in front of the tiles where that saves the round, gemm.hip.)
-                g.m = M - t0;
-                g.n = N64 - t0;
-                g.k = t0 - e0;
-                g.tri = 1;
-                g.grow0 = t0;
-                g.gcol0 = t0;
-                g.rhs_rows = (int)(M - N64);
-                PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
-                launch_gemm_sub(s, g);
-            }
-            p0 = t0;
-            next_diag_done = false;
+    const int64_t pw = std::min<int64_t>(nbo, N - p0);
+    const int64_t pe = p0 + pw;
+    bool diag_done = cy.next_diag_done; // the previous fused step (or fused update) already factored this diagonal block
+    cy.next_diag_done = false;
+    int nf = 0, nt0 = 0;    // fused steps of this panel and head tiles of the first one
+    int64_t htile = 0;
+    // head-tile scratch, two halves by panel parity: the copy into A is off the critical path
+    // (nothing before the end of the factorisation reads those tiles of A) and may still be
+    // pending on the second stream while the next panel is factored
+    double* const Hbase = c->dHead + ((p0 / nbo) & 1) * (32 * NB * NB);
+    // Will the trailing update of this panel be the fused launch that also factors the next panel's first
+    // diagonal block (k_upd_fused)?  Then the steps of this panel pre-apply their pieces of that block.
+    const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + nbo, N) < N && c->fuse_panel && c->fuse_diag
+        && c->stop_events && pw == nbo && nbo % NB == 0 && nbo >= 2 * NB && ld % 2 == 0
+        && std::min<int64_t>(nbo, N - pe) % NB == 0 && pe != stop0;
+    // the whole panel in one launch (potrf_panel.hip: k_panel256): full 256 columns, head tiles and block inverses handed over
+    // between its workgroups
+    const bool p256 = c->panel256 && c->fuse_panel && c->panel_handover && !g_batch.bt && nbo == 4 * NB && pw == nbo && pe <= M;
+    // In the first panels of a large factorisation the look-ahead stream is the longer one (N = 4096, panel 1: near + far
+    // update 30 + 84 us against 54 + 18 us of chain) and the fused next-panel update, whose 155 KB workgroups need whole CUs,
+    // ends up queued behind the far update of the panel before: releasing the stream when the PANEL is complete — its
+    // updates need nothing from the fused update — starts every near/far pair one fused update earlier.
+    hipEvent_t p_done = nullptr;
+    if (p256 && fuse_diag && c->early_bulk >= 0) {
+        const int64_t pe2_ = std::min<int64_t>(pe + nbo, N), pe3_ = std::min<int64_t>(pe2_ + nbo, N);
+        const int64_t nt128 = (N - pe3_ + 127) / 128, far_tiles = nt128 * (nt128 + 1) / 2;
+        if (pe3_ < N && far_tiles >= c->early_bulk)
+            p_done = nth_event(c->pl_events, (size_t)(p0 / nbo));
+    }
+    if (p256) {
+        double* Xt = c->dXinv + (p0 / NB) * (NB * NB);
+        if (!diag_done) {
+            PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)NB * NB * NB);
+            launch_diag(s, A + p0 + p0 * ld, ld, NB, Xt, c->dInfo, p0, 1);
         }
-        if (p0 == t0) {
-            if (la_pending) {
-                hipStreamWaitEvent(s, c->la_events[la_last], 0);
-                la_pending = false;
-            }
-            {
-                PhaseScope ps(c, GPE_PH_POTRF_TAIL, (double)(N64 - t0) * (N64 - t0) * (N64 - t0) / 3.0);
-                launch_tail(s, A, ld, t0, N64, N64, M, c->dXinv, c->dInfo, c->dTail + (c->tail_count & 1) * c->tail_cap,
-                            c->dTail + ((c->tail_count + 1) & 1) * c->tail_cap, c->gen_mode == 1 ? &gen : nullptr);
-                ++c->tail_count;
-                c->tail_lay = pl.nt_tail * 65536 + pl.nb_tail;
-            }
-            if (N64 == N)
-                break;
-            { // the ragged block and what lies under it: -= L[N64:M, t0:N64] L[N64:N, t0:N64]^T, then the panel code factors it
-                GemmArgs g{};
-                const int64_t k0 = e0 >= 0 ? e0 : t0; // (behind a tall launch: its columns too, see the update above)
-                g.C = A + N64 + N64 * ld;
-                g.ldc = ld;
-                g.A = A + N64 + k0 * ld;
-                g.lda = ld;
-                g.B = A + N64 + k0 * ld;
-                g.ldb = ld;
-                g.m = M - N64;
-                g.n = N - N64;
-                g.k = N64 - k0;
-                g.tri = 1;
-                g.grow0 = N64;
-                g.gcol0 = N64;
-                PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
-                // ONE tile with k up to 2816: dealt to up to 32 workgroups + an ordered fold (potrf_tail.hip); its scratch is the pair of polled
-                // buffers the closing launch has just used — dead until the next launch arms all of them again
-                double* const used = c->dTail + ((c->tail_count - 1) & 1) * c->tail_cap;
-                // ... and factored, inverted and its right-hand-side rows solved by the same two launches where that form serves
-                // (GPE_RAGGED_FINISH=0: the update alone, then the panel code below)
-                static const bool finish = !(getenv("GPE_RAGGED_FINISH") && atoi(getenv("GPE_RAGGED_FINISH")) == 0);
-                // (one workgroup adds the slots up here: worth it while the block is narrow — N = 520 0.156 -> 0.149 ms, 1100 0.269 ->
-                // 0.258; from ~40 columns on the sixteen workgroups of k_ragged_fold are quicker than the launches they cost)
-                if (finish && !c->prof && N - N64 <= 40
-                    && launch_ragged_finish(s, g.C, ld, g.A, ld, N - N64, M - N, g.k, used, pl.need_tail, c->dXinv + (N64 / NB) * (NB * NB),
-                                            c->dInfo, N64))
-                    break;
-                if (!launch_ragged_update(s, g.C, ld, g.A, ld, g.m, g.n, g.k, used, pl.need_tail))
-                    launch_gemm_sub(s, g);
-            }
-            p0 = N64;
-            next_diag_done = false;
+        PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - p0 - NB) * NB * NB * 2.5 * 4);
+        launch_panel256(s, A, ld, p0, M, Xt, c->dInfo, fuse_diag ? pe : -1, c->dHead + 64 * NB * NB,
+                        c->dHead + ((c->p256_count & 1) * 32 + GPE_S22_TILE) * (NB * NB),
+                        c->dHead + (((c->p256_count + 1) & 1) * 32 + GPE_S22_TILE) * (NB * NB), p_done);
+        ++c->p256_count;
+    }
+    for (int64_t j0 = p0; j0 < pe && !p256; j0 += NB) {
+        const int jb = (int)std::min<int64_t>(NB, pe - j0);
+        const int64_t r0 = j0 + jb;
+        double* Xt = c->dXinv + (j0 / NB) * (NB * NB);
+        // fused step (k_panel_step): full 64-column blocks up to the end of the panel
+        const int nt = (int)((pe - r0) / NB);
+        const bool fuse = c->fuse_panel && jb == NB && (pe - r0) % NB == 0 && r0 < M && htile + nt <= 32;
+        if (!diag_done) {
+            PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)jb * jb * jb);
+            launch_diag(s, A + j0 + j0 * ld, ld, jb, Xt, c->dInfo, j0, fuse ? 1 : 0);
         }
-        const int64_t pw = std::min<int64_t>(nbo, N - p0);
-        const int64_t pe = p0 + pw;
-        bool diag_done = next_diag_done; // the previous fused step (or fused update) already factored this diagonal block
-        next_diag_done = false;
-        int nf = 0, nt0 = 0;    // fused steps of this panel and head tiles of the first one
-        int64_t htile = 0;
-        // head-tile scratch, two halves by panel parity: the copy into A is off the critical path
-        // (nothing before the end of the factorisation reads those tiles of A) and may still be
-        // pending on the second stream while the next panel is factored
-        double* const Hbase = c->dHead + ((p0 / nbo) & 1) * (32 * NB * NB);
-        // Will the trailing update of this panel be the fused launch that also factors the next panel's first
-        // diagonal block (k_upd_fused)?  Then the steps of this panel pre-apply their pieces of that block.
-        const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + nbo, N) < N && c->fuse_panel && c->fuse_diag
-            && c->stop_events && pw == nbo && nbo % NB == 0 && nbo >= 2 * NB && ld % 2 == 0
-            && std::min<int64_t>(nbo, N - pe) % NB == 0 && pe != stop0;
-        // the whole panel in one launch (potrf_panel.hip: k_panel256): full 256 columns, head tiles and block inverses handed over
-        // between its workgroups
-        const bool p256 = c->panel256 && c->fuse_panel && c->panel_handover && !g_batch.bt && nbo == 4 * NB && pw == nbo && pe <= M;
-        // In the first panels of a large factorisation the look-ahead stream is the longer one (N = 4096, panel 1: near + far
-        // update 30 + 84 us against 54 + 18 us of chain) and the fused next-panel update, whose 155 KB workgroups need whole CUs,
-        // ends up queued behind the far update of the panel before: releasing the stream when the PANEL is complete — its
-        // updates need nothing from the fused update — starts every near/far pair one fused update earlier.
-        hipEvent_t p_done = nullptr;
-        if (p256 && fuse_diag && c->early_bulk >= 0) {
-            const int64_t pe2_ = std::min<int64_t>(pe + nbo, N), pe3_ = std::min<int64_t>(pe2_ + nbo, N);
-            const int64_t nt128 = (N - pe3_ + 127) / 128, far_tiles = nt128 * (nt128 + 1) / 2;
-            if (pe3_ < N && far_tiles >= c->early_bulk) {
-                const size_t kp = (size_t)(p0 / nbo);
-                while (c->pl_events.size() <= kp) {
-                    hipEvent_t e;
-                    hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                    c->pl_events.push_back(e);
-                }
-                p_done = c->pl_events[kp];
-            }
+        diag_done = false;
+        if (fuse) {
+            PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - r0) * NB * NB * (1 + nt));
+            if (nf == 0)
+                nt0 = nt;
+            // every step but the panel's first adds its own piece of the next panel's first diagonal block to the
+            // scratch sum (the second step starts it); the third — whose workgroup there has the most slack —
+            // also the first step's piece
+            const bool pre = fuse_diag && j0 > p0;
+            const int64_t dfirst_at = nbo >= 3 * NB ? p0 + 2 * NB : p0 + NB;
+            launch_panel_step(s, A, ld, j0, M, nt, Xt, Xt + NB * NB, nt > 0 ? 1 : 0, c->dInfo, Hbase + htile * NB * NB,
+                              pre ? pe : -1, pre && j0 == dfirst_at ? p0 : -1, j0 == p0 + NB ? 1 : 0,
+                              c->dHead + 64 * NB * NB,
+                              c->panel_handover ? (gpe_epoch_t*)(c->dHead + 65 * NB * NB) + ((p0 / nbo) & 1) * 32 + htile : nullptr);
+            htile += nt;
+            if (nt > 0)
+                ++nf;
+            diag_done = nt > 0;
+            continue;
         }
-        if (p256) {
-            double* Xt = c->dXinv + (p0 / NB) * (NB * NB);
-            if (!diag_done) {
-                PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)NB * NB * NB);
-                launch_diag(s, A + p0 + p0 * ld, ld, NB, Xt, c->dInfo, p0, 1);
-            }
-            PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - p0 - NB) * NB * NB * 2.5 * 4);
-            launch_panel256(s, A, ld, p0, M, Xt, c->dInfo, fuse_diag ? pe : -1, c->dHead + 64 * NB * NB,
-                            c->dHead + ((c->p256_count & 1) * 32 + GPE_S22_TILE) * (NB * NB),
-                            c->dHead + (((c->p256_count + 1) & 1) * 32 + GPE_S22_TILE) * (NB * NB), p_done);
-            ++c->p256_count;
+        if (r0 < M) { // L21 = A21 L11^-T, in place (each 32-row workgroup reads only its own rows)
+            GemmArgs g{};
+            g.C = A + r0 + j0 * ld;
+            g.ldc = ld;
+            g.A = A + r0 + j0 * ld;
+            g.lda = ld;
+            g.a_kmajor = 0;
+            g.B = Xt;
+            g.ldb = NB;
+            g.b_kmajor = 1; // opB(col, kk) = X[col][kk] = Xt[kk + 64 col]
+            g.m = M - r0;
+            g.n = jb;
+            g.k = jb;
+            g.overwrite = 1;
+            g.tile = 32;
+            PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - r0) * jb * jb);
+            launch_gemm_sub(s, g);
         }
-        for (int64_t j0 = p0; j0 < pe && !p256; j0 += NB) {
-            const int jb = (int)std::min<int64_t>(NB, pe - j0);
-            const int64_t r0 = j0 + jb;
-            double* Xt = c->dXinv + (j0 / NB) * (NB * NB);
-            // fused step (k_panel_step): full 64-column blocks up to the end of the panel
-            const int nt = (int)((pe - r0) / NB);
-            const bool fuse = c->fuse_panel && jb == NB && (pe - r0) % NB == 0 && r0 < M && htile + nt <= 32;
-            if (!diag_done) {
-                PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)jb * jb * jb);
-                launch_diag(s, A + j0 + j0 * ld, ld, jb, Xt, c->dInfo, j0, fuse ? 1 : 0);
-            }
-            diag_done = false;
-            if (fuse) {
-                PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - r0) * NB * NB * (1 + nt));
-                if (nf == 0)
-                    nt0 = nt;
-                // every step but the panel's first adds its own piece of the next panel's first diagonal block to the
-                // scratch sum (the second step starts it); the third — whose workgroup there has the most slack —
-                // also the first step's piece
-                const bool pre = fuse_diag && j0 > p0;
-                const int64_t dfirst_at = nbo >= 3 * NB ? p0 + 2 * NB : p0 + NB;
-                launch_panel_step(s, A, ld, j0, M, nt, Xt, Xt + NB * NB, nt > 0 ? 1 : 0, c->dInfo, Hbase + htile * NB * NB,
-                                  pre ? pe : -1, pre && j0 == dfirst_at ? p0 : -1, j0 == p0 + NB ? 1 : 0,
-                                  c->dHead + 64 * NB * NB,
-                                  c->panel_handover ? (gpe_epoch_t*)(c->dHead + 65 * NB * NB) + ((p0 / nbo) & 1) * 32 + htile : nullptr);
-                htile += nt;
-                if (nt > 0)
-                    ++nf;
-                diag_done = nt > 0;
-                continue;
-            }
-            if (r0 < M) { // L21 = A21 L11^-T, in place (each 32-row workgroup reads only its own rows)
-                GemmArgs g{};
-                g.C = A + r0 + j0 * ld;
-                g.ldc = ld;
-                g.A = A + r0 + j0 * ld;
-                g.lda = ld;
-                g.a_kmajor = 0;
-                g.B = Xt;
-                g.ldb = NB;
-                g.b_kmajor = 1; // opB(col, kk) = X[col][kk] = Xt[kk + 64 col]
-                g.m = M - r0;
-                g.n = jb;
-                g.k = jb;
-                g.overwrite = 1;
-                g.tile = 32;
-                PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - r0) * jb * jb);
-                launch_gemm_sub(s, g);
-            }
-            if (r0 < pe) { // rest of the panel's columns
-                GemmArgs g{};
-                g.C = A + r0 + r0 * ld;
-                g.ldc = ld;
-                g.A = A + r0 + j0 * ld;
-                g.lda = ld;
-                g.a_kmajor = 0;
-                g.B = A + r0 + j0 * ld;
-                g.ldb = ld;
-                g.b_kmajor = 0;
-                g.m = M - r0;
-                g.n = pe - r0;
-                g.k = jb;
-                g.tri = 1;
-                g.grow0 = r0;
-                g.gcol0 = r0;
-                PhaseScope ps(c, GPE_PH_POTRF_PANEL, gemm_flops(g));
-                launch_gemm_sub(s, g);
-            }
-        }
-        if (pe < N) { // trailing update, k = pw
-            auto upd = [&](hipStream_t st, int64_t c0, int64_t c1, int64_t rlo, int grid_limit = 0,
-                           hipEvent_t stop = nullptr, int tile = 0) {
-                // C[rlo:M, c0:c1] -= L[rlo:M, p0:pe] L[c0:c1, p0:pe]^T   (elements on/below the diagonal)
-                GemmArgs g{};
-                g.C = A + rlo + c0 * ld;
-                g.ldc = ld;
-                g.A = A + rlo + p0 * ld;
-                g.lda = ld;
-                g.B = A + c0 + p0 * ld;
-                g.ldb = ld;
-                g.m = M - rlo;
-                g.n = c1 - c0;
-                g.k = pw;
-                g.tri = 1;
-                g.grow0 = rlo;
-                g.gcol0 = c0;
-                g.grid_limit = grid_limit;
-                g.stop_event = stop;
-                g.rhs_rows = (int)(M - N); // the appended obs_mean rows: FMAs inside the direct-to-LDS kernels, not a tile row
-                if (grid_limit > 0)
-                    g.tile = tile ? tile : 128; // the direct-to-LDS kernels are the ones that honour grid_limit
-                PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
-                launch_gemm_sub(st, g);
-            };
-            const int64_t pe2 = std::min<int64_t>(pe + nbo, N);
-            if (c->lookahead && !c->prof && pe2 < N && pe != stop0) {
-                // look-ahead: the next panel's columns are updated on the main stream, the rest of the
-                // trailing matrix on the second stream while the next panel is factored
-                auto ev = [&](size_t i) {
-                    while (c->la_events.size() <= i) {
-                        hipEvent_t e;
-                        hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                        c->la_events.push_back(e);
-                    }
-                    return c->la_events[i];
-                };
-                // Events per outer panel kp: 3 kp = this panel's next-panel update done (the dispatch's own
-                // completion signal: no marker packet on the critical stream), 3 kp + 1 = the bulk update has
-                // finished the columns of panel kp + 2 ("near" part, done first), 3 kp + 2 = all of it.
-                // The main stream only ever waits for a near part, which completed most of a panel earlier:
-                // waiting for an event that fires just in time cost ~10 us per panel in the kernel trace.
-                const size_t kp = (size_t)(p0 / nbo);
-                if (la_pending)
-                    hipStreamWaitEvent(s, ev(3 * (kp - 1) + 1), 0); // the previous bulk update also wrote these columns
-                if (fuse_diag) {
-                    // the update and, underneath it in the same launch, the factorisation of the next panel's
-                    // first diagonal block (k_upd_fused): no k_diag launch at the head of the next panel
-                    GemmArgs g{};
-                    g.C = A + pe + pe * ld;
-                    g.ldc = ld;
-                    g.A = A + pe + p0 * ld;
-                    g.lda = ld;
-                    g.B = A + pe + p0 * ld;
-                    g.ldb = ld;
-                    g.m = M - pe;
-                    g.n = pe2 - pe;
-                    g.k = pw;
-                    g.tri = 1;
-                    g.grow0 = pe;
-                    g.gcol0 = pe;
-                    g.stop_event = ev(3 * kp);
-                    launch_upd_fused(s, g, A, ld, pe, pe, c->dXinv + (pe / NB) * (NB * NB), c->dInfo,
-                                     c->dHead + 64 * NB * NB); // the steps summed the pieces: no products here
-                    next_diag_done = true;
-                }
-                else if (c->stop_events)
-                    upd(s, pe, pe2, pe, 0, ev(3 * kp));
-                else { // GPE_STOP_EVENT=0: a marker packet instead (rocprofv3's kernel trace delays dispatches
-                       // that carry their own completion event by ~100 us; use this form under the profiler)
-                    upd(s, pe, pe2, pe);
-                    hipEventRecord(ev(3 * kp), s);
-                }
-                hipStreamWaitEvent(c->stream2, p_done ? p_done : ev(3 * kp), 0); // the bulk update starts now and shares the
-                                                               // chip with panel kp + 1 only (p_done: and with this update)
-                if (nf > 0 && !c->panel_handover) // (with the hand-over the head tiles were written in place too)
-                    launch_head_copy(c->stream2, A, ld, p0, nt0, nf, Hbase);
-                nf = 0;
-                const int64_t pe3 = std::min<int64_t>(pe2 + nbo, N);
-                upd(c->stream2, pe2, pe3, pe2, c->near_wgs >= 0 ? c->near_wgs : c->bulk_wgs, nullptr, 64); // near: what panel kp + 1's update needs
-                hipEventRecord(ev(3 * kp + 1), c->stream2);
-                if (pe3 < N) {
-                    // 1 looping workgroup per CU on bulk_wgs CUs leaves 256 - bulk_wgs CUs to the panel.  When the update
-                    // is many times longer than a panel (large trailing matrices: N = 16384 has 8 k tiles in its first
-                    // ones) the reserve idles most of the time: above bulk_free_tiles tiles the update is dispatched
-                    // unrestricted and the panel's workgroups take CUs as tiles retire (43.4 -> 34.6 ms at N = 16384)
-                    const int64_t nt128 = (N - pe3 + 127) / 128, far_tiles = nt128 * (nt128 + 1) / 2;
-                    upd(c->stream2, pe3, N, pe3, far_tiles >= c->bulk_free_tiles ? 0 : c->bulk_wgs);
-                }
-                hipEventRecord(ev(3 * kp + 2), c->stream2);
-                la_pending = true;
-                la_last = 3 * kp + 2;
-            }
-            else {
-                if (la_pending) {
-                    hipStreamWaitEvent(s, c->la_events[la_last], 0);
-                    la_pending = false;
-                }
-                if (nf > 0 && !c->panel_handover)
-                    launch_head_copy(s, A, ld, p0, nt0, nf, Hbase);
-                nf = 0;
-                upd(s, pe, N, pe);
-            }
-        }
-        if (nf > 0 && !c->panel_handover) { // last panel: no trailing update
-            PhaseScope ps(c, GPE_PH_POTRF_PANEL, 0.0);
-            launch_head_copy(s, A, ld, p0, nt0, nf, Hbase);
-            nf = 0;
+        if (r0 < pe) { // rest of the panel's columns
+            const GemmArgs g = tri_update(A, ld, M, r0, r0, pe, j0, r0);
+            PhaseScope ps(c, GPE_PH_POTRF_PANEL, gemm_flops(g));
+            launch_gemm_sub(s, g);
         }
     }
-    if (la_pending)
-        hipStreamWaitEvent(s, c->la_events[la_last], 0);
+    // the head tiles of the fused steps into A (with the hand-over they were written in place): at most once per panel
+    auto head_copy = [&](hipStream_t st) {
+        if (nf > 0 && !c->panel_handover)
+            launch_head_copy(st, A, ld, p0, nt0, nf, Hbase);
+        nf = 0;
+    };
+    if (pe < N) { // trailing update, k = pw
+        // columns [c0, c1), rows from rlo on
+        auto upd = [&](hipStream_t st, int64_t c0, int64_t c1, int64_t rlo, hipEvent_t stop = nullptr) {
+            GemmArgs g = tri_update(A, ld, M, rlo, c0, c1, p0, pe);
+            g.stop_event = stop;
+            g.rhs_rows = (int)(M - N); // the appended obs_mean rows: FMAs inside the direct-to-LDS kernels, not a tile row
+            PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
+            launch_gemm_sub(st, g);
+        };
+        const int64_t pe2 = std::min<int64_t>(pe + nbo, N);
+        if (c->lookahead && !c->prof && pe2 < N && pe != stop0) {
+            // look-ahead: the next panel's columns are updated on the main stream, the rest of the
+            // trailing matrix on the second stream while the next panel is factored
+            auto ev = [&](size_t i) { return nth_event(c->la_events, i); };
+            // Events per outer panel kp: 3 kp = this panel's next-panel update done (the dispatch's own
+            // completion signal: no marker packet on the critical stream), 3 kp + 1 = the bulk update has
+            // finished the columns of panel kp + 2 ("near" part, done first), 3 kp + 2 = all of it.
+            // The main stream only ever waits for a near part, which completed most of a panel earlier:
+            // waiting for an event that fires just in time cost ~10 us per panel in the kernel trace.
+            const size_t kp = (size_t)(p0 / nbo);
+            if (cy.la_pending)
+                hipStreamWaitEvent(s, ev(3 * (kp - 1) + 1), 0); // the previous bulk update also wrote these columns
+            if (fuse_diag) {
+                // the update and, underneath it in the same launch, the factorisation of the next panel's
+                // first diagonal block (k_upd_fused): no k_diag launch at the head of the next panel
+                GemmArgs g = tri_update(A, ld, M, pe, pe, pe2, p0, pe);
+                g.stop_event = ev(3 * kp);
+                launch_upd_fused(s, g, A, ld, pe, pe, c->dXinv + (pe / NB) * (NB * NB), c->dInfo,
+                                 c->dHead + 64 * NB * NB); // the steps summed the pieces: no products here
+                cy.next_diag_done = true;
+            }
+            else if (c->stop_events)
+                upd(s, pe, pe2, pe, ev(3 * kp));
+            else { // GPE_STOP_EVENT=0: a marker packet instead (rocprofv3's kernel trace delays dispatches
+                   // that carry their own completion event by ~100 us; use this form under the profiler)
+                upd(s, pe, pe2, pe);
+                hipEventRecord(ev(3 * kp), s);
+            }
+            hipStreamWaitEvent(c->stream2, p_done ? p_done : ev(3 * kp), 0); // the bulk update starts now and shares the
+                                                           // chip with panel kp + 1 only (p_done: and with this update)
+            head_copy(c->stream2);
+            const int64_t pe3 = std::min<int64_t>(pe2 + nbo, N);
+            upd(c->stream2, pe2, pe3, pe2); // near: what panel kp + 1's update needs
+            hipEventRecord(ev(3 * kp + 1), c->stream2);
+            if (pe3 < N) // far: dispatched unrestricted, the panel's workgroups take CUs as tiles retire (holding CUs back for
+                         // the panel lost: 43.4 -> 34.6 ms at N = 16384, 640 -> 651/s at 4096, profiles/r03_chain_study.md)
+                upd(c->stream2, pe3, N, pe3);
+            hipEventRecord(ev(3 * kp + 2), c->stream2);
+            cy.la_pending = true;
+            cy.la_last = 3 * kp + 2;
+        }
+        else {
+            cy.join(c, s);
+            head_copy(s);
+            upd(s, pe, N, pe);
+        }
+    }
+    if (nf > 0 && !c->panel_handover) { // last panel: no trailing update
+        PhaseScope ps(c, GPE_PH_POTRF_PANEL, 0.0);
+        head_copy(s);
+    }
+}
+
+// The tall data-flow launch over [e0, t0), every row strip below riding along, and its ONE update of everything behind t0.
+static void potrf_tall(gpe_ctx* c, double* A, int64_t M, const TailPlan& pl, const TailGen& gen, PotrfCarry& cy)
+{
+    hipStream_t s = c->stream;
+    const int64_t ld = c->ld, e0 = pl.e0, t0 = pl.t0, N64 = pl.N64;
+    cy.join(c, s);
+    {
+        const double w = (double)(t0 - e0), h = (double)(M - e0);
+        PhaseScope ps(c, GPE_PH_POTRF_TALL, w * w * w / 3.0 + (h - w) * w * w);
+        double* pair = c->dTail + 2 * c->tail_cap;
+        launch_tail(s, A, ld, e0, t0, N64, M, c->dXinv, c->dInfo, pair + (c->tall_count & 1) * c->tall_cap,
+                    pair + ((c->tall_count + 1) & 1) * c->tall_cap, c->gen_mode == 2 ? &gen : nullptr);
+        if (c->gen_mode == 2 && c->gen_ev) // the rest of K, built on the second stream beside this launch
+            hipStreamWaitEvent(s, c->gen_ev, 0);
+        ++c->tall_count;
+        c->tall_lay = pl.nt_tall * 65536 + pl.nb_tall;
+    }
+    // everything behind t0 -= L[t0:M, e0:t0] L[t0:N64, e0:t0]^T: one launch, k = t0 - e0.
+    // (A ragged order: the columns of its last block, N64 .. N, stay out of this launch — they would be a 23rd column of
+    // 128 x 128 tiles at N = 4100, a second round of the chip, 214 -> 337 us — and take the tall launch's columns together
+    // with the closing launch's in their own update (potrf_closing).  The rows under N64 — the ragged rows and the right-hand
+    // sides — are the launch's "right-hand-side rows": plain FMAs in front of the tiles where that saves the round, gemm.hip.)
+    GemmArgs g = tri_update(A, ld, M, t0, t0, N64, e0, t0);
+    g.rhs_rows = (int)(M - N64);
+    PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
+    launch_gemm_sub(s, g);
+    cy.next_diag_done = false;
+}
+
+// The closing data-flow launch over [t0, N64) and, for a ragged order, the update of the last block (N64 .. N, fewer than 64
+// columns) and of what lies under it.  Returns whether the factorisation is complete: false — the panel code factors the
+// ragged block.
+static bool potrf_closing(gpe_ctx* c, double* A, int64_t N, int64_t M, const TailPlan& pl, const TailGen& gen, PotrfCarry& cy)
+{
+    hipStream_t s = c->stream;
+    const int64_t ld = c->ld, e0 = pl.e0, t0 = pl.t0, N64 = pl.N64;
+    cy.join(c, s);
+    {
+        PhaseScope ps(c, GPE_PH_POTRF_TAIL, (double)(N64 - t0) * (N64 - t0) * (N64 - t0) / 3.0);
+        launch_tail(s, A, ld, t0, N64, N64, M, c->dXinv, c->dInfo, c->dTail + (c->tail_count & 1) * c->tail_cap,
+                    c->dTail + ((c->tail_count + 1) & 1) * c->tail_cap, c->gen_mode == 1 ? &gen : nullptr);
+        ++c->tail_count;
+        c->tail_lay = pl.nt_tail * 65536 + pl.nb_tail;
+    }
+    if (N64 == N)
+        return true;
+    // -= L[N64:M, k0:N64] L[N64:N, k0:N64]^T (behind a tall launch: its columns too, see potrf_tall)
+    const GemmArgs g = tri_update(A, ld, M, N64, N64, N, e0 >= 0 ? e0 : t0, N64);
+    PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
+    // ONE tile with k up to 2816: dealt to up to 32 workgroups + an ordered fold (potrf_tail.hip); its scratch is the pair of polled
+    // buffers the closing launch has just used — dead until the next launch arms all of them again
+    double* const used = c->dTail + ((c->tail_count - 1) & 1) * c->tail_cap;
+    // ... and factored, inverted and its right-hand-side rows solved by the same two launches where that form serves
+    // (GPE_RAGGED_FINISH=0: the update alone, then the panel code)
+    static const bool finish = env_not_zero("GPE_RAGGED_FINISH");
+    // (one workgroup adds the slots up here: worth it while the block is narrow — N = 520 0.156 -> 0.149 ms, 1100 0.269 ->
+    // 0.258; from ~40 columns on the sixteen workgroups of k_ragged_fold are quicker than the launches they cost)
+    if (finish && !c->prof && N - N64 <= 40
+        && launch_ragged_finish(s, g.C, ld, g.A, ld, N - N64, M - N, g.k, used, pl.need_tail, c->dXinv + (N64 / NB) * (NB * NB),
+                                c->dInfo, N64))
+        return true;
+    if (!launch_ragged_update(s, g.C, ld, g.A, ld, g.m, g.n, g.k, used, pl.need_tail))
+        launch_gemm_sub(s, g);
+    cy.next_diag_done = false;
+    return false;
+}
+
+// The factorisation of one evaluation under plan pl (compute_enqueue made it and prepared its buffers).
+// The last <= tail_max columns (all of them when N <= tail_max) go to ONE launch, a tiled data-flow factorisation
+// (potrf_tail.hip: k_tail): the panels end at t0.  Its columns are whole 64-blocks: t0 .. N64; a ragged last block and the
+// right-hand-side rows ride in it as one more row strip.  Round 4: up to tall_max columns in front of t0 are one launch of the
+// same kernel too (e0 .. t0), followed by ONE update of everything behind t0 with k = t0 - e0; 256-column panels with look-ahead
+// only in front of e0 (none at N = 4096: three launches factor the matrix).
+void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M, const TailPlan& pl)
+{
+    PotrfCarry cy;
+    const int64_t stop0 = pl.e0 >= 0 ? pl.e0 : pl.t0; // where the panels end in front of a data-flow launch (< 0: at N)
+    for (int64_t p0 = 0; p0 < (stop0 >= 0 ? stop0 : N); p0 += c->nbo)
+        potrf_panel(c, A, N, M, p0, stop0, cy);
+    if (pl.t0 >= 0) {
+        // gen_mode (compute_enqueue): the first data-flow launch generates its tiles of K itself — nobody built them
+        const TailGen gen{c->dXt, c->ld, N, c->dOm, c->ld, (c->flow_solve && (N + NB - 1) / NB <= 256) ? c->dAl : nullptr, c->ld, c->P, &c->kp};
+        if (pl.e0 >= 0)
+            potrf_tall(c, A, M, pl, gen, cy);
+        if (!potrf_closing(c, A, N, M, pl, gen, cy))
+            potrf_panel(c, A, N, M, pl.N64, stop0, cy);
+    }
+    cy.join(c, c->stream);
 }
 
 // Z <- L^-1 B in place, B is N x M (ldb).  identity_structure: B starts as the identity, so at
@@ -566,7 +530,7 @@ void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int6
 // shape — the caller takes k_trsv_bwd_flow
 static bool bwd_chain_sweep(gpe_ctx* c, hipStream_t s, const double* y, int64_t ysi, double* al, int prefilled, const double* om, double* part)
 {
-    static const bool on = !(getenv("GPE_SWEEP_M") && atoi(getenv("GPE_SWEEP_M")) == 0);
+    static const bool on = env_not_zero("GPE_SWEEP_M");
     const int64_t nblk = (c->N + NB - 1) / NB;
     // (below eight blocks the two matrix-core products in front of the chain cost what the shorter hops save: N = 256 0.077 against 0.075 ms)
     if (!on || g_batch.bt || g_batch.G != 1 || nblk < 8 || nblk > 256)
@@ -653,46 +617,46 @@ int compute_enqueue(gpe_ctx* c)
 {
     if (c->N <= 0 || !c->dA)
         return GPE_ERR_STATE;
+    if (c->handover_off_left > 0 && --c->handover_off_left == 0)
+        c->panel_handover = c->panel_handover_cfg; // re-armed after a run of clean evaluations without it (in front of the plan, which reads it)
+    // The plan of this evaluation's factorisation: made once, here.  A single handle's hand-over buffers are reserved in front of
+    // the gate (reserve_tail) and prepared behind it; a batched sequence's were prepared by batch_enqueue_fused.
+    TailPlan pl = tail_plan(c, c->N, c->N + c->P);
+    bool may_partition = false;
+    if (!g_batch.bt) {
+        may_partition = pl.t0 == 0 || (pl.t0 > 0 && pl.e0 == 0); // data-flow launches from column 0 on: no 256-column panels
+        (void)reserve_tail(c, pl, c->stream); // (a failure shows again, and is handled, where the buffers are prepared)
+    }
     // One evaluation's chain of launches as a unit behind the device's previous data-flow launch (dev.h: FlowGate; the gates of
     // the launches below nest inside this one): two handles evaluated from two threads run chain behind chain — 840
     // evaluations/s in all at N = 4096, where gating launch by launch interleaved their chains at 600.  Not for a batched
     // sequence: the two sub-batches of a batch of 64 overlap on purpose (their data-flow launches are still ordered one by one).
     // Round 5: when another chain is in flight on the device, this one goes to one of two CU-masked streams instead — half
     // of every XCD's CUs each — and the two run side by side (ChainScope, below).
-    bool may_partition = false;
-    if (!g_batch.bt) {
-        const TailPlan pl0 = tail_plan(c, c->N, c->N + c->P);
-        may_partition = pl0.t0 == 0 || (pl0.t0 > 0 && pl0.e0 == 0); // data-flow launches from column 0 on: no 256-column panels
-        (void)reserve_tail(c, pl0, c->stream); // (a failure shows again, and is handled, where the buffers are prepared)
-    }
     ChainScope gate(c, !g_batch.bt, may_partition);
     hipStream_t s = c->stream; // (the handle's own stream, or the partition's for the length of this enqueue)
     if (gate.part >= 0)
         c->inv_early = false; // (its events would make the own stream wait for a masked one: see ChainScope's destructor)
     digest_kernel(c);
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
-    if (c->handover_off_left > 0 && --c->handover_off_left == 0)
-        c->panel_handover = c->panel_handover_cfg; // re-armed after a run of clean evaluations without it
+    if (pl.t0 >= 0 && !g_batch.bt && !prepare_tail(c, pl, s))
+        pl = TailPlan{}; // (no buffers: by panels to the end)
     const bool flow_al = c->flow_solve && (c->N + NB - 1) / NB <= 256;
     bool rows_done = false; // obs_mean^T under the matrix + the sweep's sentinel: by the build launch itself where it can
     // Round 4: where the data-flow launches begin decides whether K is built at all.  When the first of them starts at
     // column 0 it generates its tiles itself (potrf_tail.hip: tail_gen_tile): for N <= 2560 the kernel matrix is never written,
     // for the tall launch of N = 4096 only the 2560 x 2560 block behind it is — beside the tall launch, on the second stream.
+    // GPE_TAIL_GEN: 0 never; 1 (default) when ONE launch is the whole factorisation (N <= 2560: 0.489 -> 0.477 ms at
+    // N = 2048, 0.254 -> 0.247 at 1024); 2 / 3: also the tall launch of N <= 4096, the block behind it built on the second
+    // stream beside it / on the main stream in front of it — measured at N = 4096: 2 LOSES (1.253 -> 1.272 ms: the build
+    // takes CUs from the first columns of the chain and the update then waits for an event)
+    static const int gen_lvl = (int)env_int("GPE_TAIL_GEN", 1);
     c->gen_mode = 0;
-    {
-        // GPE_TAIL_GEN: 0 never; 1 (default) when ONE launch is the whole factorisation (N <= 2560: 0.489 -> 0.477 ms at
-        // N = 2048, 0.254 -> 0.247 at 1024); 2 / 3: also the tall launch of N <= 4096, the block behind it built on the second
-        // stream beside it / on the main stream in front of it — measured at N = 4096: 2 LOSES (1.253 -> 1.272 ms: the build
-        // takes CUs from the first columns of the chain and the update then waits for an event)
-        static const int gen_lvl = getenv("GPE_TAIL_GEN") ? atoi(getenv("GPE_TAIL_GEN")) : 1;
-        const TailPlan pl = tail_plan(c, c->N, c->N + c->P);
-        const int64_t N64 = c->N / NB * NB;
-        if (gen_lvl > 0 && !c->host_K && !c->prof && pl.t0 >= 0 && (g_batch.bt || prepare_tail(c, pl, s))) {
-            if (pl.t0 == 0 && (N64 == c->N || !g_batch.bt))
-                c->gen_mode = 1;
-            else if (pl.e0 == 0 && !g_batch.bt && gen_lvl >= 2)
-                c->gen_mode = 2;
-        }
+    if (gen_lvl > 0 && !c->host_K && !c->prof && pl.t0 >= 0) {
+        if (pl.t0 == 0 && (c->N % NB == 0 || !g_batch.bt))
+            c->gen_mode = 1;
+        else if (pl.e0 == 0 && !g_batch.bt && gen_lvl >= 2)
+            c->gen_mode = 2;
     }
     if (c->host_K) {
         if (!c->dKhost)
@@ -704,14 +668,12 @@ int compute_enqueue(gpe_ctx* c)
         project_lambda(c, s, c->dXt, c->ld, 0, c->N);
         // what is left to build: the ragged last block (mode 1) / everything behind the tall launch (mode 2), with
         // obs_mean's rows and the sweep's sentinel for those columns
-        const TailPlan pl = tail_plan(c, c->N, c->N + c->P);
         const int64_t b0 = c->gen_mode == 1 ? c->N / NB * NB : pl.t0;
         rows_done = true;
         if (b0 < c->N) {
             const BuildRowsTail rt{c->dOm + b0, c->ld, c->P, c->dA + c->N + b0 * c->ld, flow_al ? c->dAl + b0 : nullptr, 0};
             hipStream_t sb = s;
-            static const bool beside = !(getenv("GPE_TAIL_GEN") && atoi(getenv("GPE_TAIL_GEN")) == 3);
-            if (c->gen_mode == 2 && c->kp.k_lam == 0 && beside) { // beside the tall launch (nothing of this handle is in flight on stream2)
+            if (c->gen_mode == 2 && c->kp.k_lam == 0 && gen_lvl != 3) { // beside the tall launch (nothing of this handle is in flight on stream2)
                 sb = c->stream2;
                 if (!c->gen_ev)
                     hipEventCreateWithFlags(&c->gen_ev, hipEventDisableTiming);
@@ -731,7 +693,7 @@ int compute_enqueue(gpe_ctx* c)
         PhaseScope ps(c, GPE_PH_KERNEL_BUILD, 0.0);
         project_lambda(c, s, c->dXt, c->ld, 0, c->N);
         const BuildRowsTail rt{c->dOm, c->ld, c->P, c->dA + c->N, flow_al ? c->dAl : nullptr, 0};
-        static const bool tail = !(getenv("GPE_ROWS_TAIL") && atoi(getenv("GPE_ROWS_TAIL")) == 0);
+        static const bool tail = env_not_zero("GPE_ROWS_TAIL");
         rows_done = launch_build_K(s, c->dXt, c->ld, c->N, c->kp, c->dA, c->ld, tail ? &rt : nullptr);
     }
     if (c->gen_mode == 0) {
@@ -739,7 +701,7 @@ int compute_enqueue(gpe_ctx* c)
             launch_cols_to_rows(s, c->dOm, c->ld, c->N, c->P, c->dA + c->N, c->ld, flow_al ? c->dAl : nullptr);
         c->al_prefilled = flow_al;
     }
-    potrf_blocked(c, c->dA, c->N, c->N + c->P);
+    potrf_blocked(c, c->dA, c->N, c->N + c->P, pl);
     c->have_L = true;
     c->inv_ok = false; // gp.hpp:570
     inv2_start_early(c);
@@ -801,7 +763,7 @@ static hipError_t wait_chain(gpe_ctx* c)
 // answers it by running the same work again with one launch per block (GPE_FLOW_FAULT=1 forces that path in tests).
 static bool flow_failed(gpe_ctx* c)
 {
-    static const bool fault = getenv("GPE_FLOW_FAULT") && atoi(getenv("GPE_FLOW_FAULT")) != 0;
+    static const bool fault = env_flag("GPE_FLOW_FAULT", false);
     const bool bad = c->hInfo[1] != 0 || (fault && c->flow_solve);
     if (c->hInfo[1] != 0)
         partitions_give_up("a sweep's hand-off timed out");

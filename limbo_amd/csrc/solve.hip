@@ -209,7 +209,7 @@ static __device__ __forceinline__ double flow_sum(const double (&p)[W][NB], int 
 }
 unsigned flow_grid(int64_t nblk)
 {
-    static const bool xcd = !(getenv("GPE_FLOW_XCD") && atoi(getenv("GPE_FLOW_XCD")) == 0);
+    static const bool xcd = env_not_zero("GPE_FLOW_XCD");
     return (unsigned)(xcd ? 8 * nblk : nblk);
 }
 #define FW 8            // waves per workgroup of the data-flow sweep (16 measured no better)
@@ -846,12 +846,6 @@ __global__ void k_zero_upper(double* __restrict__ A, int64_t lda, int64_t n)
     const int64_t j = blockIdx.y;
     if (i < n && i < j)
         A[i + j * lda] = 0.0;
-}
-void launch_zero_upper(hipStream_t s, double* A, int64_t lda, int64_t n)
-{
-    if (n <= 0)
-        return;
-    GPE_LAUNCH(k_zero_upper, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, s, A, lda, n);
 }
 
 // A[i][j] = A[j][i] for i < j (32x32 LDS-transposed tiles so both sides are coalesced)
