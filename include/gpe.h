@@ -245,6 +245,9 @@ int gpe_debug_tri_tile_map(int64_t m, int64_t n, int64_t grow0, int64_t gcol0, i
  * data-flow launch; -1: panels to the end), e0 (first column of the tall launch in front of it; -1: none), tile columns and row
  * strips of the closing launch, of the tall launch, n rounded down to 64, outer panel width }. */
 int gpe_debug_tail_plan(int64_t n, int p, int g, int64_t tail_max, int64_t tall_max, int64_t batch_tail_max, int64_t* out8);
+/* Test hook, host only: the device buffers the handles of this process own right now (csrc/devbuf.h) and their bytes.  The
+ * streams, the scratch block and the pinned block that a destroyed handle leaves to the next one are not among them. */
+int gpe_debug_live_buffers(int64_t* count, int64_t* bytes);
 /* Test hook, host only: the launch plan of the recursive K^-1 (csrc/inv2.hip; replaces the dense solves of gp.hpp:254-264) for
  * order n and leading dimension ld (>= n rounded up to 64), dealt into nbins shares (<= 0: 512) with chunk-length factor
  * load_pct / 100 (<= 0: 1.0); nbins < 0: the plan of a batched sequence of -nbins members.  One row of 16 int64 per tile product, in

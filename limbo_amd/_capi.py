@@ -100,6 +100,7 @@ def _sig(lib, prefix):
             "hbm_stream_peak": [C.c_int, _dp],
             "epoch": [_vp, C.POINTER(C.c_uint64)],
             "xproc_waits": [C.POINTER(_i64)],
+            "debug_live_buffers": [C.POINTER(_i64), C.POINTER(_i64)],
             # include/gpe_joint.h: the joint posterior over a point batch
             "joint_query": [_vp, _dp, _i64, C.c_double, _dp, _dp, _i64],
             "joint_draws": [_vp, _dp, _i64, C.c_double, _dp, _dp, C.c_int, _dp, C.POINTER(_i64), _dp],
@@ -571,6 +572,14 @@ def device_count(lib) -> int:
 def append_max_chunk(lib) -> int:
     """gpe_append_max_chunk: rows the device tail of gpe_add_samples factorises at once."""
     return int(lib.fn("append_max_chunk")())
+
+
+def debug_live_buffers(lib):
+    """gpe_debug_live_buffers: (count, bytes) of the device buffers this process's handles own right now."""
+    n, b = _i64(0), _i64(0)
+    if lib.fn("debug_live_buffers")(C.byref(n), C.byref(b)) != 0:
+        raise EngineError("debug_live_buffers failed")
+    return n.value, b.value
 
 
 def debug_append_slices(lib, n):

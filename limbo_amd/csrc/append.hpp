@@ -135,8 +135,7 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
         if (e)
             return e;
     }
-    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * c->ld, obs_mean, sizeof(double) * nfin, sizeof(double) * nfin, P,
-                               hipMemcpyHostToDevice, s));
+    HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, nfin, nfin, P, s));
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
     {
         const int e = append_enqueue(c, Xb, nb0, rem, extra, slices_cap);

@@ -57,27 +57,16 @@ static int batch_enqueue_fused(gpe_ctx** cs, int Gc, BatchTab** tab_out, const B
     if (want && want->grad) { // every member needs the same three buffers before the table is built
         for (int q = 0; q < Gc; ++q) {
             gpe_ctx* c = cs[q];
-            const size_t mat = sizeof(double) * (size_t)(c->ld * c->cap);
-            if (!c->dLinv) {
-                HIPCHK(c, hipMalloc(&c->dLinv, mat));
-                c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-            }
-            if (!c->dKinv)
-                HIPCHK(c, hipMalloc(&c->dKinv, mat));
-            const int bufs_needed = Gc >= 4 ? 1 : 1 + inv2_partials(); // (inv2_prepare's rule: a batch of >= 4 cuts no k range)
-            if (c->dInvS && c->invS_bufs < bufs_needed) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                hipFree(c->dInvS);
-                c->dInvS = nullptr;
-            }
-            if (!c->dInvS && inv2_supported(c->N)) { // the recursive K^-1's scratch (inv2.hip)
-                HIPCHK(c, hipMalloc(&c->dInvS, mat * (size_t)bufs_needed));
-                c->invS_bufs = bufs_needed;
-                c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-            }
+            int rc = reserve_mat(c, c->dLinv);
+            if (!rc)
+                rc = reserve_mat(c, c->dKinv);
+            if (!rc) // (inv2_prepare's rule: a batch of >= 4 cuts no k range)
+                rc = reserve_invS(c, Gc >= 4 ? 1 : 1 + inv2_partials());
+            if (rc)
+                return rc;
             if (inv2_supported(c->N))
                 inv2_zero_pads(c, c0->stream); // (every member's, on the stream the batch runs on)
-            int rc = ensure_grad_partial(c, want->n_grad);
+            rc = ensure_grad_partial(c, want->n_grad);
             if (rc)
                 return rc;
         }
@@ -113,12 +102,10 @@ static int batch_enqueue_fused(gpe_ctx** cs, int Gc, BatchTab** tab_out, const B
         gpe_ctx* c = cs[q];
         digest_kernel(c);
         c->hInfo[0] = c->hInfo[1] = 0;
-        const char* b[GPE_BT_CLS] = {(const char*)c->dA, (const char*)c->dXt, (const char*)c->dOm, (const char*)c->dAl,
-                                     (const char*)c->dXinv, (const char*)c->dHead, (const char*)c->hInfo, (const char*)c->hScal,
-                                     (const char*)c->dLinv, (const char*)c->dKinv, (const char*)c->dGradPartial, (const char*)c->dTail,
-                                     (const char*)c->dInvS};
+        const void* b[GPE_BT_CLS] = {c->dA, c->dXt, c->dOm, c->dAl, c->dXinv, c->dHead, c->hInfo, c->hScal, c->dLinv, c->dKinv, c->dGradPartial,
+                                     c->dTail, c->dInvS};
         for (int k = 0; k < GPE_BT_CLS; ++k)
-            t.base[k][q] = b[k];
+            t.base[k][q] = (const char*)b[k];
         t.kp[q] = c->kp;
         hipStreamSynchronize(c->stream); // nothing of this handle may still be in flight on its own stream
     }
@@ -127,7 +114,7 @@ static int batch_enqueue_fused(gpe_ctx** cs, int Gc, BatchTab** tab_out, const B
                                                (unsigned long long)(dbl * c0->ld * c0->P), (unsigned long long)(dbl * c0->ld * c0->P),
                                                (unsigned long long)(dbl * (c0->cap / NB) * NB * NB), (unsigned long long)(dbl * GPE_HEAD_TILES * NB * NB), 64, 8192,
                                                (unsigned long long)(c0->dLinv ? dbl * c0->ld * c0->cap : 0), (unsigned long long)(c0->dKinv ? dbl * c0->ld * c0->cap : 0),
-                                               (unsigned long long)(c0->dGradPartial ? dbl * c0->grad_partial_cap : 0),
+                                               (unsigned long long)(dbl * c0->dGradPartial.capacity()),
                                                (unsigned long long)(c0->dTail ? dbl * 2 * (c0->tail_cap + c0->tall_cap) : 0),
                                                (unsigned long long)(c0->dInvS ? dbl * c0->ld * c0->cap * (Gc >= 4 ? 1 : 1 + inv2_partials()) : 0)};
     for (int k = 0; k < GPE_BT_CLS; ++k) {

@@ -21,6 +21,7 @@
 #include "../../include/gpe_sparse_grad.h"
 #include "../../include/gpe_query_grad.h"
 #include "dev.h"
+#include "devbuf.h"
 
 #include <algorithm>
 #include <cmath>
@@ -100,6 +101,7 @@ struct PhaseRec {
 } // namespace
 
 struct gpe_ctx {
+    DEVBUF_LOCAL ~gpe_ctx() = default; // (frees what free_dev has not; not an exported symbol)
     std::atomic<uint64_t> epoch{1}; // bumped by every call that can change what a query answers (gpe_epoch: round 6 — the C++ drop-in's
                                     // per-device query replicas are valid exactly as long as this has not moved)
     int device = 0;  // physical HIP device
@@ -123,7 +125,7 @@ struct gpe_ctx {
     // the polled hand-over buffers of the data-flow launches, ONE allocation: [closing 0 | closing 1 | tall 0 | tall 1].  Of a
     // pair, the buffer of parity `count & 1` is armed (all-ones) for the slot layout of the pair's previous launch; a launch
     // with another layout (another N or P on this handle) first puts the whole pair back to all-ones (prepare_tail)
-    double* dTail = nullptr;
+    DevBuf<double> dTail;
     int64_t tail_cap = 0, tall_cap = 0; // doubles per buffer of the closing / tall pair
     unsigned tail_count = 0, tall_count = 0;
     int64_t tail_lay = -1, tall_lay = -1; // nt * 65536 + nb of the pair's previous launch (-1: both buffers entirely all-ones)
@@ -144,20 +146,22 @@ struct gpe_ctx {
     double theta[GPE_MAX_THETA] = {0};
     double noise = 0.01; // defaults::kernel::noise (kernel/kernel.hpp:57)
     KParams kp;
-    double *dXt = nullptr, *dA = nullptr, *dOm = nullptr, *dAl = nullptr, *dW = nullptr, *dY = nullptr;
-    double *dLinv = nullptr, *dKinv = nullptr, *dKhost = nullptr, *dGradPartial = nullptr, *dGrad = nullptr;
-    double *dLooS = nullptr, *dLooV = nullptr; // leave-one-out scratch: N x N and N x (P + 2) (+8)
-    double* dQuery = nullptr; // query scratch kept between calls while it is small (single-point queries: no malloc/free)
-    size_t query_bytes = 0;
-    double* dHead = nullptr; // scratch tiles of the fused panel steps (k_panel_step)
+    // Device memory: every DevBuf is owned by the handle (devbuf.h); the raw pointers beside them are views or the shell's.
+    DevBuf<double> dXt, dA, dOm, dAl, dW, dY; // alloc_dev's: sized by (cap, D, P)
+    DevBuf<double> dLinv, dKinv, dKhost;      // ld x cap each, on demand (reserve_mat)
+    DevBuf<double> dGradPartial;              // scratch of the pair-sum kernel + the gradient behind it (ensure_grad_partial)
+    double* dGrad = nullptr;                  // view: the last gradient, inside dGradPartial
+    DevBuf<double> dLooS, dLooV; // leave-one-out scratch: N x N and N x (P + 2) (+8)
+    DevBuf<double> dQuery; // query scratch kept between calls while it is small (single-point queries: no malloc/free)
+    double* dHead = nullptr; // view: scratch tiles of the fused panel steps (k_panel_step), inside dScal's block
     bool panel_handover = true; // head tiles of a panel step change hands (potrf_panel.hip); GPE_PANEL_HANDOVER=0: re-derived
     bool panel_handover_cfg = true; // what the caller / environment chose: a hand-over timeout switches panel_handover off
     int handover_off_left = 0;      // ... for this many evaluations only, then it is re-armed (one hiccup is not forever)
     int64_t handover_reruns = 0;    // evaluations re-run after a hand-over timeout (gpe_handover_reruns)
-    double* dXinv = nullptr; // transposed inverses of the 64 x 64 diagonal blocks of L, 4096 doubles each
+    DevBuf<double> dXinv; // transposed inverses of the 64 x 64 diagonal blocks of L, 4096 doubles each
     bool panel256 = true;    // all steps of a 256-column outer panel in one data-flow launch (GPE_PANEL256=0: step by step)
-    double* dXp = nullptr;   // inverses of the nbo x nbo diagonal panels of L, compact (ensure_inv with the overlapped product)
-    double* dInvS = nullptr; // the recursive K^-1's scratch (inv2.hip): T-forms / W | three partial buffers, ld x cap each
+    DevBuf<double> dXp;      // inverses of the nbo x nbo diagonal panels of L, compact (ensure_inv with the overlapped product)
+    DevBuf<double> dInvS;    // the recursive K^-1's scratch (inv2.hip): T-forms / W | three partial buffers, ld x cap each
     int invS_bufs = 0;       // ... how many ld x cap buffers it holds: 1 + inv2_partials() for a single handle, 1 for a member of a
                              // batch of >= 4 (whose plan cuts no k range: ADVICE r5 — 64 x N = 4096 used to reserve 26 GB it never touched)
     Inv2Plan* inv2 = nullptr; // ... and its plan, rebuilt when N, ld or a buffer changes
@@ -168,20 +172,18 @@ struct gpe_ctx {
     bool inv_early = false;   // set by gpe_hp_objective around compute_enqueue: start K^-1's lowest level beside the sweep
     bool inv_prefix_done = false; // ... done on stream2 for the factor at hand; inv_ev completes behind it
     hipEvent_t inv_ev = nullptr, inv_ev0 = nullptr;
-    size_t xp_cap = 0;
-    int64_t grad_partial_cap = 0;
-    int* dInfo = nullptr; // = hInfo: pinned host memory the kernels write directly (no copy-back, no device memset)
-    double* dScal = nullptr; // [0] sum log L_ii, [1] trace(om^T alpha), [2] knn scratch, [8 .. 8 + 2 nblk) per-block partials
+    int* dInfo = nullptr; // view: = hInfo, pinned host memory the kernels write directly (no copy-back, no device memset)
+    double* dScal = nullptr; // the HandleShell's device block (gpe_create / gpe_destroy): [0] sum log L_ii, [1] trace(om^T alpha), [2] knn scratch, [8 .. 8 + 2 nblk) per-block partials
     int ll_partials = 0;     // > 0: the backward sweep left that many per-block partial sums instead of [0], [1]
     bool al_prefilled = false; // alpha holds the sentinel pattern of the data-flow sweep
-    int* hInfo = nullptr;    // pinned
-    double* hScal = nullptr; // pinned
+    int* hInfo = nullptr;    // view: hPinned + 0
+    double* hScal = nullptr; // view: hPinned + 128
     bool have_L = false, inv_ok = false, host_K = false, ll_ok = false;
     int nbo = 256; // outer panel width of the two-level blocked algorithms
     // one-launch small-N path (small.hip): pinned staging the kernels read / write directly, the word the host spins on
-    char* hPinned = nullptr;             // the one pinned allocation behind hInfo / hSmallSeq / hScal / hSmall
-    double* hSmall = nullptr;            // [0..2): log-lik terms | [16 .. 16+8*GPE_MAX_P+8): kta, var | [256..): obs_mean / query points in
-    unsigned long long* hSmallSeq = nullptr; // 8 sequence words (one per query point; word 0 for add_sample)
+    char* hPinned = nullptr;             // the HandleShell's pinned allocation behind hInfo / hSmallSeq / hScal / hSmall
+    double* hSmall = nullptr;            // view: hScal + 1024.  [0..2): log-lik terms | [16 .. 16+8*GPE_MAX_P+8): kta, var | [256..): obs_mean / query points in
+    unsigned long long* hSmallSeq = nullptr; // view: hPinned + 64.  8 sequence words (one per query point; word 0 for add_sample)
     unsigned long long small_seq = 0;
     bool small_path = true;              // GPE_SMALL=0 disables
     int64_t small_calls = 0;             // calls served by the small path (instrumentation / tests)
@@ -316,32 +318,35 @@ int lam_columns(int kind, int n_theta, int D)
     return k <= max_lam(D) ? k : -1;
 }
 
+// rows x cols doubles out of an ld-strided column-major matrix, device to host and host to device; with a stream the Async
+// form on it, without one the blocking form
+hipError_t copy2d(hipMemcpyKind kind, double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t s)
+{
+    const size_t b = sizeof(double);
+    return s ? hipMemcpy2DAsync(dst, b * (size_t)ldd, src, b * (size_t)lds, b * (size_t)rows, (size_t)cols, kind, s)
+             : hipMemcpy2D(dst, b * (size_t)ldd, src, b * (size_t)lds, b * (size_t)rows, (size_t)cols, kind);
+}
+hipError_t copy2d_to_host(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t s = nullptr)
+{
+    return copy2d(hipMemcpyDeviceToHost, dst, ldd, src, lds, rows, cols, s);
+}
+hipError_t copy2d_from_host(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t cols, hipStream_t s = nullptr)
+{
+    return copy2d(hipMemcpyHostToDevice, dst, ldd, src, lds, rows, cols, s);
+}
+
+// everything sized by (cap, D, P) or by the data; dTail (sized by the plan) stays until gpe_destroy
 void free_dev(gpe_ctx* c)
 {
-    double** ps[] = {&c->dXt, &c->dA, &c->dOm, &c->dAl, &c->dW, &c->dY, &c->dLinv, &c->dKinv, &c->dKhost,
-                     &c->dGradPartial, &c->dXinv, &c->dLooS, &c->dLooV};
-    for (auto p : ps) {
-        if (*p)
-            hipFree(*p);
-        *p = nullptr;
-    }
-    if (c->dQuery)
-        hipFree(c->dQuery);
-    c->dQuery = nullptr;
-    c->query_bytes = 0;
-    if (c->dXp)
-        hipFree(c->dXp);
-    c->dXp = nullptr;
-    c->xp_cap = 0;
-    if (c->dInvS)
-        hipFree(c->dInvS);
-    c->dInvS = nullptr;
+    for (DevBuf<double>* b : {&c->dXt, &c->dA, &c->dOm, &c->dAl, &c->dW, &c->dY, &c->dLinv, &c->dKinv, &c->dKhost, &c->dGradPartial, &c->dXinv,
+                              &c->dLooS, &c->dLooV, &c->dQuery, &c->dXp, &c->dInvS})
+        b->reset();
+    c->dGrad = nullptr;
     c->invS_bufs = 0;
     c->inv_pad_n = -1;
     inv2_plan_free(c->inv2);
     inv2_plan_free(c->inv2_batched);
     c->inv2 = c->inv2_batched = nullptr;
-    c->grad_partial_cap = 0;
     c->cap = c->ld = 0;
 }
 
@@ -353,20 +358,47 @@ int alloc_dev(gpe_ctx* c, int64_t cap, int D, int P)
     int64_t ld = ld_for(cap, P);
     c->cap = cap;
     c->ld = ld;
-    HIPCHK(c, hipMalloc(&c->dXt, sizeof(double) * (size_t)(ld * xt_rows(D))));
-    HIPCHK(c, hipMalloc(&c->dA, sizeof(double) * (size_t)(ld * cap)));
-    HIPCHK(c, hipMalloc(&c->dOm, sizeof(double) * (size_t)(ld * P)));
-    HIPCHK(c, hipMalloc(&c->dAl, sizeof(double) * (size_t)(ld * P)));
-    HIPCHK(c, hipMalloc(&c->dW, sizeof(double) * (size_t)(ld * std::max(P, 1))));
-    HIPCHK(c, hipMalloc(&c->dY, sizeof(double) * (size_t)(ld * std::max(P, 1))));
-    HIPCHK(c, hipMalloc(&c->dXinv, sizeof(double) * (size_t)(cap / NB) * NB * NB));
+    HIPCHK(c, c->dXt.reserve((size_t)(ld * xt_rows(D))));
+    HIPCHK(c, c->dA.reserve((size_t)(ld * cap)));
+    HIPCHK(c, c->dOm.reserve((size_t)(ld * P)));
+    HIPCHK(c, c->dAl.reserve((size_t)(ld * P)));
+    HIPCHK(c, c->dW.reserve((size_t)(ld * std::max(P, 1))));
+    HIPCHK(c, c->dY.reserve((size_t)(ld * std::max(P, 1))));
+    HIPCHK(c, c->dXinv.reserve((size_t)(cap / NB) * NB * NB));
     HIPCHK(c, hipMemsetAsync(c->dXinv, 0, sizeof(double) * (size_t)(cap / NB) * NB * NB, c->stream));
     HIPCHK(c, hipMemsetAsync(c->dXt, 0, sizeof(double) * (size_t)(ld * xt_rows(D)), c->stream));
     return GPE_OK;
 }
 
+// an ld x cap matrix of the handle's, on demand: dLinv, dKinv, dLooS, dKhost.  Whatever changes ld x cap has reset them
+int reserve_mat(gpe_ctx* c, DevBuf<double>& m)
+{
+    if (m)
+        return GPE_OK;
+    HIPCHK(c, m.reserve((size_t)(c->ld * c->cap)));
+    if (&m == &c->dLinv)
+        c->inv_pad_n = -1; // (fresh memory under U: the pads of the recursive K^-1 are to be zero-filled)
+    return GPE_OK;
+}
+
+// the recursive K^-1's scratch (inv2.hip) with room for `bufs` ld x cap buffers, where the order takes the recursion
+int reserve_invS(gpe_ctx* c, int bufs)
+{
+    if (c->dInvS && c->invS_bufs < bufs) { // (a member of an earlier batch, now evaluated alone)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->dInvS.reset();
+    }
+    if (!c->dInvS && inv2_supported(c->N)) {
+        HIPCHK(c, c->dInvS.reserve((size_t)(c->ld * c->cap) * (size_t)bufs));
+        c->invS_bufs = bufs;
+        c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
+    }
+    return GPE_OK;
+}
+
 // grow capacity keeping X, L, Om (add_sample path; the reference reallocates K and L on every
-// add_sample — gp.hpp:581,:588 conservativeResize — here capacity doubles)
+// add_sample — gp.hpp:581,:588 conservativeResize — here capacity doubles).  The new buffers are locals until the copies are
+// done: an early return frees them, the swap at the end hands the old ones to the locals' destructors.
 int grow_dev(gpe_ctx* c, int64_t need)
 {
     if (need <= c->cap)
@@ -374,14 +406,14 @@ int grow_dev(gpe_ctx* c, int64_t need)
     int64_t ncap = round_up(std::max<int64_t>(need, 2 * c->cap), NB);
     int D = c->D, P = c->P;
     int64_t nld = ld_for(ncap, P);
-    double *nXt = nullptr, *nA = nullptr, *nOm = nullptr, *nAl = nullptr, *nW = nullptr, *nY = nullptr, *nXi = nullptr;
-    HIPCHK(c, hipMalloc(&nXt, sizeof(double) * (size_t)(nld * xt_rows(D))));
-    HIPCHK(c, hipMalloc(&nA, sizeof(double) * (size_t)(nld * ncap)));
-    HIPCHK(c, hipMalloc(&nOm, sizeof(double) * (size_t)(nld * P)));
-    HIPCHK(c, hipMalloc(&nAl, sizeof(double) * (size_t)(nld * P)));
-    HIPCHK(c, hipMalloc(&nW, sizeof(double) * (size_t)(nld * P)));
-    HIPCHK(c, hipMalloc(&nY, sizeof(double) * (size_t)(nld * P)));
-    HIPCHK(c, hipMalloc(&nXi, sizeof(double) * (size_t)(ncap / NB) * NB * NB));
+    DevBuf<double> nXt, nA, nOm, nAl, nW, nY, nXi;
+    HIPCHK(c, nXt.reserve((size_t)(nld * xt_rows(D))));
+    HIPCHK(c, nA.reserve((size_t)(nld * ncap)));
+    HIPCHK(c, nOm.reserve((size_t)(nld * P)));
+    HIPCHK(c, nAl.reserve((size_t)(nld * P)));
+    HIPCHK(c, nW.reserve((size_t)(nld * P)));
+    HIPCHK(c, nY.reserve((size_t)(nld * P)));
+    HIPCHK(c, nXi.reserve((size_t)(ncap / NB) * NB * NB));
     HIPCHK(c, hipMemsetAsync(nXi, 0, sizeof(double) * (size_t)(ncap / NB) * NB * NB, c->stream));
     HIPCHK(c, hipMemsetAsync(nXt, 0, sizeof(double) * (size_t)(nld * xt_rows(D)), c->stream));
     if (c->N > 0) {
@@ -391,20 +423,19 @@ int grow_dev(gpe_ctx* c, int64_t need)
                        c->stream);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    double* old[] = {c->dXt, c->dA, c->dOm, c->dAl, c->dW, c->dY, c->dLinv, c->dKinv, c->dXinv, c->dLooS, c->dLooV, c->dInvS};
-    for (double* p : old)
-        if (p)
-            hipFree(p);
-    c->dInvS = nullptr;
+    c->dXt.swap(nXt);
+    c->dA.swap(nA);
+    c->dOm.swap(nOm);
+    c->dAl.swap(nAl);
+    c->dW.swap(nW);
+    c->dY.swap(nY);
+    c->dXinv.swap(nXi);
+    // what was sized by the old ld x cap and holds nothing a grown handle may use: again on demand.  dKhost among them — a
+    // handle that was given K, then a kernel, then samples kept the old-sized buffer, and the next gpe_set_K_host wrote
+    // N x N at the new ld into it
+    for (DevBuf<double>* b : {&c->dLinv, &c->dKinv, &c->dLooS, &c->dLooV, &c->dInvS, &c->dKhost})
+        b->reset();
     c->invS_bufs = 0;
-    c->dXt = nXt;
-    c->dA = nA;
-    c->dOm = nOm;
-    c->dAl = nAl;
-    c->dW = nW;
-    c->dY = nY;
-    c->dXinv = nXi;
-    c->dLinv = c->dKinv = c->dLooS = c->dLooV = nullptr;
     c->inv_pad_n = -1;
     c->inv_ok = false;
     c->cap = ncap;
@@ -596,6 +627,16 @@ int gpe_create(int device_id, gpe_handle* out)
             // the hand-over flag words start from zero, in the order of the stream the panel steps run on
             || hipMemsetAsync(c->dScal + 1024 + 65 * NB * NB, 0, sizeof(double) * NB * NB, c->stream) != hipSuccess
             || hipHostMalloc(&c->hPinned, 128 + 8192 + sizeof(double) * SMALL_STAGE_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)) {
+        if (c->stream)
+            hipStreamSynchronize(c->stream); // (the memset, if it got that far)
+        if (c->hPinned)
+            hipHostFree(c->hPinned);
+        if (c->dScal)
+            hipFree(c->dScal);
+        if (c->stream2)
+            hipStreamDestroy(c->stream2);
+        if (c->stream)
+            hipStreamDestroy(c->stream);
         delete c;
         return GPE_ERR_HIP;
     }
@@ -677,8 +718,7 @@ int gpe_destroy(gpe_handle c)
     for (auto e : c->pool)
         hipEventDestroy(e);
     free_dev(c);
-    if (c->dTail)
-        hipFree(c->dTail);
+    c->dTail.reset();
     for (auto e : c->pl_events)
         hipEventDestroy(e);
     for (auto e : c->la_events)
@@ -726,19 +766,8 @@ int gpe_set_data(gpe_handle c, const double* X, int64_t N, int D, const double* 
         if (rc)
             return rc;
     }
-    if (c->dLinv) {
-        hipFree(c->dLinv);
-        c->dLinv = nullptr;
-    }
-    if (c->dKinv) {
-        hipFree(c->dKinv);
-        c->dKinv = nullptr;
-    }
-    for (double** q : {&c->dLooS, &c->dLooV})
-        if (*q) {
-            hipFree(*q);
-            *q = nullptr;
-        }
+    for (DevBuf<double>* b : {&c->dLinv, &c->dKinv, &c->dLooS, &c->dLooV}) // K^-1 and what hangs on it: again on demand
+        b->reset();
     c->N = N;
     c->D = D;
     c->P = P;
@@ -748,8 +777,7 @@ int gpe_set_data(gpe_handle c, const double* X, int64_t N, int D, const double* 
     double* tmp = c->dA;
     HIPCHK(c, hipMemcpyAsync(tmp, X, sizeof(double) * (size_t)(N * D), hipMemcpyHostToDevice, c->stream));
     launch_transpose_x(c->stream, tmp, N, D, c->dXt, c->ld, 0);
-    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * c->ld, obs_mean, sizeof(double) * N, sizeof(double) * N, P,
-                               hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, N, N, P, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return GPE_OK;
 }
@@ -805,10 +833,9 @@ int gpe_set_K_host(gpe_handle c, const double* K, int64_t ldk)
     {
         std::lock_guard<std::mutex> lk(c->mu);
     }
-    if (!c->dKhost)
-        HIPCHK(c, hipMalloc(&c->dKhost, sizeof(double) * (size_t)(c->ld * c->cap)));
-    HIPCHK(c, hipMemcpy2D(c->dKhost, sizeof(double) * c->ld, K, sizeof(double) * ldk, sizeof(double) * c->N, c->N,
-                          hipMemcpyHostToDevice));
+    if (int rc = reserve_mat(c, c->dKhost))
+        return rc;
+    HIPCHK(c, copy2d_from_host(c->dKhost, c->ld, K, ldk, c->N, c->N));
     c->host_K = true;
     c->kind = GPE_KERNEL_HOST_K;
     return GPE_OK;
@@ -883,8 +910,7 @@ int gpe_update_alpha(gpe_handle c, const double* obs_mean)
         return GPE_OK;
     }
     if (obs_mean)
-        HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * c->ld, obs_mean, sizeof(double) * c->N,
-                                   sizeof(double) * c->N, c->P, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, c->N, c->N, c->P, c->stream));
     solve_alpha(c);
     enqueue_loglik_terms(c);
     int rc = compute_finish(c);
@@ -985,12 +1011,11 @@ static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* o
     HIPCHK(c, hipMemcpyAsync(c->dY, x, sizeof(double) * D, hipMemcpyHostToDevice, s));
     launch_transpose_x(s, c->dY, 1, D, c->dXt, ld, n);
     project_lambda(c, s, c->dXt, ld, n, 1);
-    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * ld, obs_mean, sizeof(double) * ldo,
-                               sizeof(double) * (n + 1), P, hipMemcpyHostToDevice, s));
+    HIPCHK(c, copy2d_from_host(c->dOm, ld, obs_mean, ldo, n + 1, P, s));
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
     // k(x_i, x_new) for i = 0..n (gp.hpp:583-586), no noise yet
     launch_build_Ks(s, c->dXt, ld, n + 1, c->dXt + n, ld, 1, c->kp, c->dW, ld);
-    GPE_LAUNCH(k_knn, dim3(1), dim3(1), 0, s, c->dW, n, c->kp.diag_add, c->dScal + 2);
+    GPE_LAUNCH(k_knn, dim3(1), dim3(1), 0, s, c->dW.get(), n, c->kp.diag_add, c->dScal + 2);
     auto new_row = [c, s, n, ld] {
         PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)n * n);
         if (n > 0) {
@@ -999,7 +1024,7 @@ static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* o
                 launch_trsv_fwd_flow(s, c->dA, ld, n, c->dXinv, c->dW, ld, c->dY, ld, 1, c->dInfo + 1);
             else
                 launch_trsv_sweep(s, c->dA, ld, n, c->dXinv, c->dW, c->dY, ld, 1, 0);
-            GPE_LAUNCH(k_vec_to_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->dY, c->dA + n, ld,
+            GPE_LAUNCH(k_vec_to_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->dY.get(), c->dA + n, ld,
                                n);
         }
         launch_append_diag(s, c->dA + n, ld, n, c->dScal + 2, c->dInfo); // gp.hpp:596-597
@@ -1251,8 +1276,7 @@ int gpe_set_obs_mean(gpe_handle c, const double* obs_mean)
         return GPE_ERR_ARG;
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipMemcpy2DAsync(c->dOm, sizeof(double) * c->ld, obs_mean, sizeof(double) * c->N, sizeof(double) * c->N,
-                               c->P, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, c->N, c->N, c->P, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ll_ok = false;
     return GPE_OK;
@@ -1276,8 +1300,7 @@ int gpe_get_L(gpe_handle c, double* L, int64_t ldh)
     std::lock_guard<std::mutex> lk(c->mu);
     const int64_t N = c->N;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(L, sizeof(double) * ldh, c->dA, sizeof(double) * c->ld, sizeof(double) * N, N,
-                          hipMemcpyDeviceToHost));
+    HIPCHK(c, copy2d_to_host(L, ldh, c->dA, c->ld, N, N));
     for (int64_t j = 1; j < N; ++j) // matrixL(): zero upper triangle (gp.hpp:411)
         memset(L + j * ldh, 0, sizeof(double) * (size_t)j);
     return GPE_OK;
@@ -1291,8 +1314,7 @@ int gpe_set_L(gpe_handle c, const double* L, int64_t ldh)
         return GPE_ERR_ARG;
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipMemcpy2D(c->dA, sizeof(double) * c->ld, L, sizeof(double) * ldh, sizeof(double) * c->N, c->N,
-                          hipMemcpyHostToDevice));
+    HIPCHK(c, copy2d_from_host(c->dA, c->ld, L, ldh, c->N, c->N));
     launch_diag_inv(c->stream, c->dA, c->ld, c->N, 0, (c->N + NB - 1) / NB, c->dXinv);
     if (!c->host_K && lam_columns(c->kind, c->n_theta, c->D) > 0) {
         // compute() never ran on this handle: the Lambda^T x rows of the training samples that the cross-kernel
@@ -1316,8 +1338,7 @@ int gpe_get_alpha(gpe_handle c, double* a)
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(a, sizeof(double) * c->N, c->dAl, sizeof(double) * c->ld, sizeof(double) * c->N, c->P,
-                          hipMemcpyDeviceToHost));
+    HIPCHK(c, copy2d_to_host(a, c->N, c->dAl, c->ld, c->N, c->P));
     return GPE_OK;
 }
 
@@ -1329,8 +1350,7 @@ int gpe_set_alpha(gpe_handle c, const double* a)
         return GPE_ERR_ARG;
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
-    HIPCHK(c, hipMemcpy2D(c->dAl, sizeof(double) * c->ld, a, sizeof(double) * c->N, sizeof(double) * c->N, c->P,
-                          hipMemcpyHostToDevice));
+    HIPCHK(c, copy2d_from_host(c->dAl, c->ld, a, c->N, c->N, c->P));
     c->ll_ok = false;
     return GPE_OK;
 }
@@ -1347,8 +1367,7 @@ int gpe_get_Kinv(gpe_handle c, double* Kinv, int64_t ldh)
     const int64_t N = c->N;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     drain_phases(c);
-    HIPCHK(c, hipMemcpy2D(Kinv, sizeof(double) * ldh, c->dKinv, sizeof(double) * c->ld, sizeof(double) * N, N,
-                          hipMemcpyDeviceToHost));
+    HIPCHK(c, copy2d_to_host(Kinv, ldh, c->dKinv, c->ld, N, N));
     for (int64_t j = 1; j < N; ++j) // mirror the lower triangle
         for (int64_t i = 0; i < j; ++i)
             Kinv[i + j * ldh] = Kinv[j + i * ldh];
@@ -1385,12 +1404,9 @@ int gpe_get_loo_weights(gpe_handle c, double* W, int64_t ldh)
         drain_phases(c);
         c->hInfo[1] = 0;
     }
-    HIPCHK(c, hipMemcpy2D(W, sizeof(double) * ldh, c->dLinv, sizeof(double) * c->ld, sizeof(double) * N, N,
-                          hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy2D(u.data(), sizeof(double) * N, c->dLooV, sizeof(double) * c->ld, sizeof(double) * N, P,
-                          hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy2D(a.data(), sizeof(double) * N, c->dAl, sizeof(double) * c->ld, sizeof(double) * N, P,
-                          hipMemcpyDeviceToHost));
+    HIPCHK(c, copy2d_to_host(W, ldh, c->dLinv, c->ld, N, N));
+    HIPCHK(c, copy2d_to_host(u.data(), N, c->dLooV, c->ld, N, P));
+    HIPCHK(c, copy2d_to_host(a.data(), N, c->dAl, c->ld, N, P));
     for (int64_t j = 0; j < N; ++j)
         for (int64_t i = j; i < N; ++i) {
             double w = -W[i + j * ldh];
@@ -1411,21 +1427,16 @@ int gpe_get_K(gpe_handle c, double* K, int64_t ldh)
     if (c->host_K) {
         if (!c->dKhost)
             return GPE_ERR_STATE;
-        HIPCHK(c, hipMemcpy2D(K, sizeof(double) * ldh, c->dKhost, sizeof(double) * c->ld, sizeof(double) * N, N,
-                              hipMemcpyDeviceToHost));
+        HIPCHK(c, copy2d_to_host(K, ldh, c->dKhost, c->ld, N, N));
         return GPE_OK;
     }
     digest_kernel(c);
-    double* tmp = nullptr;
-    HIPCHK(c, hipMalloc(&tmp, sizeof(double) * (size_t)(c->ld * N)));
+    DevBuf<double> tmp;
+    HIPCHK(c, tmp.reserve((size_t)(c->ld * N)));
     project_lambda(c, c->stream, c->dXt, c->ld, 0, N);
     launch_build_K_full(c->stream, c->dXt, c->ld, N, c->kp, tmp, c->ld);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpy2D(K, sizeof(double) * ldh, tmp, sizeof(double) * c->ld, sizeof(double) * N, N,
-                        hipMemcpyDeviceToHost);
-    hipFree(tmp);
-    HIPCHK(c, e);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, copy2d_to_host(K, ldh, tmp, c->ld, N, N));
     return GPE_OK;
 }
 
@@ -1530,12 +1541,17 @@ int gpe_clone_to(gpe_handle src, int device_id, gpe_handle* out)
         copy(c->dOm, src->dOm, sizeof(double) * (size_t)(c->ld * c->P));
         copy(c->dAl, src->dAl, sizeof(double) * (size_t)(c->ld * c->P));
         copy(c->dXinv, src->dXinv, sizeof(double) * (size_t)(c->cap / NB) * NB * NB);
-        if (src->dKhost) {
-            hipMalloc(&c->dKhost, mat);
-            copy(c->dKhost, src->dKhost, mat);
+        if (src->dKhost)
+            rc = reserve_mat(c, c->dKhost);
+        if (rc == GPE_OK && src->inv_ok && src->dKinv)
+            rc = reserve_mat(c, c->dKinv);
+        if (rc) {
+            gpe_destroy(c);
+            return rc;
         }
-        if (src->inv_ok && src->dKinv) {
-            hipMalloc(&c->dKinv, mat);
+        if (c->dKhost)
+            copy(c->dKhost, src->dKhost, mat);
+        if (c->dKinv) {
             copy(c->dKinv, src->dKinv, mat);
             c->inv_ok = true;
         }
@@ -1702,6 +1718,14 @@ int gpe_trace_dump(const char* path)
     return GPE_OK;
 }
 
+int gpe_debug_live_buffers(int64_t* count, int64_t* bytes)
+{
+    if (!count || !bytes)
+        return GPE_ERR_ARG;
+    *count = DevBufLive::count.load();
+    *bytes = DevBufLive::bytes.load();
+    return GPE_OK;
+}
 int gpe_debug_tail_order(int nt, int nb, int lag, int pair) { return debug_tail_order(nt, nb, lag, pair); }
 int gpe_debug_ragged_split(int64_t k, int64_t scratch_doubles, int* kc)
 {

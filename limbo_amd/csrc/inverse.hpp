@@ -22,23 +22,13 @@ static void inv2_zero_pads(gpe_ctx* c, hipStream_t s)
 static int inv2_prepare(gpe_ctx* c)
 {
     const int64_t ld = c->ld;
-    if (!c->dLinv) {
-        HIPCHK(c, hipMalloc(&c->dLinv, sizeof(double) * (size_t)(ld * c->cap)));
-        c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-    }
-    if (!c->dKinv)
-        HIPCHK(c, hipMalloc(&c->dKinv, sizeof(double) * (size_t)(ld * c->cap)));
-    const int bufs_needed = g_batch.G >= 4 ? 1 : 1 + inv2_partials(); // (the plan of a batch of >= 4 cuts no k range: no partial buffers)
-    if (c->dInvS && c->invS_bufs < bufs_needed) { // (a member of an earlier batch, now evaluated alone)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->dInvS);
-        c->dInvS = nullptr;
-    }
-    if (!c->dInvS) {
-        HIPCHK(c, hipMalloc(&c->dInvS, sizeof(double) * (size_t)(ld * c->cap) * (size_t)bufs_needed));
-        c->invS_bufs = bufs_needed;
-        c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-    }
+    int rc = reserve_mat(c, c->dLinv);
+    if (!rc)
+        rc = reserve_mat(c, c->dKinv);
+    if (!rc) // (the plan of a batch of >= 4 cuts no k range: no partial buffers)
+        rc = reserve_invS(c, g_batch.G >= 4 ? 1 : 1 + inv2_partials());
+    if (rc)
+        return rc;
     Inv2Plan*& slot = g_batch.G >= 4 ? c->inv2_batched : c->inv2;
     bool rebuilt = false;
     slot = inv2_plan_get(slot, c->N, ld, c->dA, c->dLinv, c->dKinv, c->dInvS, ld * c->cap, g_batch.G, &rebuilt);
@@ -77,17 +67,16 @@ int ensure_inv(gpe_ctx* c)
         return GPE_ERR_STATE;
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld;
-    if (!c->dLinv) {
-        HIPCHK(c, hipMalloc(&c->dLinv, sizeof(double) * (size_t)(ld * c->cap)));
-        c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-    }
-    if (!c->dKinv)
-        HIPCHK(c, hipMalloc(&c->dKinv, sizeof(double) * (size_t)(ld * c->cap)));
+    int rc = reserve_mat(c, c->dLinv);
+    if (!rc)
+        rc = reserve_mat(c, c->dKinv);
+    if (rc)
+        return rc;
     if (inv2_supported(N)) {
         // Round 5: the recursion of inv2.hip — a dozen launches of tile-product lists with k = 256 .. N / 2 instead of 48
         // launches of k = 256 (N >= 1024, ragged orders included; smaller ones keep the panel form below).  A batched sequence runs the
         // same lists for every member (gridDim.z; batch_enqueue_fused allocated every member's scratch).
-        int rc = inv2_prepare(c);
+        rc = inv2_prepare(c);
         if (rc)
             return rc;
         {
@@ -126,14 +115,8 @@ int ensure_inv(gpe_ctx* c)
         // Batched launches, profiling runs and GPE_INV_OVERLAP=0 keep everything on one stream, product last, as before.
         static const bool overlap_ok = env_not_zero("GPE_INV_OVERLAP");
         const bool overlap = overlap_ok && !g_batch.bt && !c->prof && c->stop_events && npan >= 4;
-        if (overlap && (int64_t)c->xp_cap < npan * nbo * nbo) {
-            if (c->dXp)
-                hipFree(c->dXp);
-            c->dXp = nullptr;
-            c->xp_cap = 0;
-            HIPCHK(c, hipMalloc(&c->dXp, sizeof(double) * (size_t)(npan * nbo * nbo)));
-            c->xp_cap = (size_t)(npan * nbo * nbo);
-        }
+        if (overlap)
+            HIPCHK(c, c->dXp.reserve((size_t)(npan * nbo * nbo)));
         auto ev = [&](size_t i) {
             while (c->la_events.size() <= i) {
                 hipEvent_t e;
@@ -262,11 +245,8 @@ int ensure_inv(gpe_ctx* c)
 
 static int ensure_loo_bufs(gpe_ctx* c, bool square)
 {
-    if (!c->dLooV)
-        HIPCHK(c, hipMalloc(&c->dLooV, sizeof(double) * (size_t)(c->ld * (c->P + 2) + 8)));
-    if (square && !c->dLooS)
-        HIPCHK(c, hipMalloc(&c->dLooS, sizeof(double) * (size_t)(c->ld * c->cap)));
-    return GPE_OK;
+    HIPCHK(c, c->dLooV.reserve((size_t)(c->ld * (c->P + 2) + 8)));
+    return square ? reserve_mat(c, c->dLooS) : GPE_OK;
 }
 
 // Weights of the leave-one-out gradient (grad.hip header; gp.hpp:354-402): on return
@@ -279,10 +259,9 @@ static int loo_weights(gpe_ctx* c)
         return rc;
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld;
-    if (!c->dLinv) { // a clone that inherited K^-1 never ran ensure_inv's allocation
-        HIPCHK(c, hipMalloc(&c->dLinv, sizeof(double) * (size_t)(ld * c->cap)));
-        c->inv_pad_n = -1; // (fresh memory: the pads of the recursive K^-1 are to be zero-filled)
-    }
+    rc = reserve_mat(c, c->dLinv); // (a clone that inherited K^-1 never ran ensure_inv's allocation)
+    if (rc)
+        return rc;
     double *v = c->dLooV, *sc = c->dLooV + ld * c->P, *val = sc + ld, *outp = c->dLooV + ld * (c->P + 2);
     {
         PhaseScope ps(c, GPE_PH_GRAD, 0.0);
@@ -320,15 +299,7 @@ static int loo_weights(gpe_ctx* c)
 // scratch of the pair-sum kernel (grad.hip) + the T outputs behind it
 static int ensure_grad_partial(gpe_ctx* c, int n_grad)
 {
-    const int64_t need = grad_partial_size(c->N, n_grad) + GPE_MAX_THETA + 8;
-    if (need > c->grad_partial_cap) {
-        if (c->dGradPartial)
-            hipFree(c->dGradPartial);
-        c->dGradPartial = nullptr;
-        c->grad_partial_cap = 0;
-        HIPCHK(c, hipMalloc(&c->dGradPartial, sizeof(double) * (size_t)need));
-        c->grad_partial_cap = need;
-    }
+    HIPCHK(c, c->dGradPartial.reserve((size_t)(grad_partial_size(c->N, n_grad) + GPE_MAX_THETA + 8)));
     return GPE_OK;
 }
 

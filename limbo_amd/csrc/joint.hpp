@@ -17,6 +17,27 @@ static int64_t joint_max_points(const gpe_ctx* c)
 // kernels, compute_enqueue copies it under the factor, so Sigma survives a failed factorisation), one all-zero right-hand side
 // (the engine requires P >= 1), D = 1 — created lazily on the model's device, re-used while M fits, freed with the handle, never
 // cloned.  Its evaluations go through compute_enqueue / compute_finish like anybody's: the same gate, lock scopes and re-runs.
+// (shared with the sparse model's scratch, sparse.hpp) a dense context shaped for order M and P right-hand sides with the kernel
+// kind "K is given" and room for that K; *fresh: its buffers are new, nothing of an earlier order is in them
+static int scratch_with_K(gpe_ctx* sc, int64_t M, int P, bool* fresh)
+{
+    *fresh = M > sc->cap || P != sc->P || !sc->dA || !sc->dKhost;
+    if (*fresh) {
+        int rc = alloc_dev(sc, M, 1, P);
+        if (rc == GPE_OK)
+            rc = reserve_mat(sc, sc->dKhost);
+        if (rc)
+            return rc;
+        sc->D = 1;
+        sc->P = P;
+    }
+    sc->N = M;
+    sc->kind = GPE_KERNEL_HOST_K;
+    sc->host_K = true;
+    sc->have_L = sc->inv_ok = sc->ll_ok = false;
+    sc->prof = false;
+    return GPE_OK;
+}
 static int joint_scratch(gpe_ctx* c, int64_t M, gpe_ctx** out)
 {
     if (!c->joint) {
@@ -28,25 +49,15 @@ static int joint_scratch(gpe_ctx* c, int64_t M, gpe_ctx** out)
         c->joint = sc;
     }
     gpe_ctx* sc = c->joint;
-    if (M > sc->cap || !sc->dA || !sc->dKhost) {
-        if (alloc_dev(sc, M, 1, 1) != GPE_OK) {
-            c->err = "joint posterior: " + sc->err;
-            return GPE_ERR_NOMEM;
-        }
-        if (hipMalloc(&sc->dKhost, sizeof(double) * (size_t)(sc->ld * sc->cap)) != hipSuccess) {
-            c->err = "joint posterior: no memory for the covariance";
-            return GPE_ERR_NOMEM;
-        }
+    bool fresh = false;
+    if (scratch_with_K(sc, M, 1, &fresh) != GPE_OK) {
+        c->err = "joint posterior: " + sc->err;
+        return GPE_ERR_NOMEM;
+    }
+    if (fresh) { // the one all-zero right-hand side
         HIPCHK(c, hipMemsetAsync(sc->dOm, 0, sizeof(double) * (size_t)sc->ld, sc->stream));
         HIPCHK(c, hipStreamSynchronize(sc->stream));
-        sc->D = 1;
-        sc->P = 1;
     }
-    sc->N = M;
-    sc->kind = GPE_KERNEL_HOST_K;
-    sc->host_K = true;
-    sc->have_L = sc->inv_ok = sc->ll_ok = false;
-    sc->prof = false;
     *out = sc;
     return GPE_OK;
 }
@@ -214,8 +225,7 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     }
     mark(2);
     if (cov)
-        HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(double) * (size_t)ldc, sc->dKhost, sizeof(double) * (size_t)sc->ld, sizeof(double) * (size_t)M,
-                                   (size_t)M, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, copy2d_to_host(cov, ldc, sc->dKhost, sc->ld, M, M, s));
     if (dr && ncols > 0) {
         HIPCHK(c, hipMemcpyAsync(dZn, dr->Z, sizeof(double) * n_z, hipMemcpyHostToDevice, s));
         if (n_mq)

@@ -45,11 +45,9 @@ static void qg_columns(gpe_ctx* c, const double* Qt, int64_t ldq, int64_t mc, in
                           dG, mc_max);
     }
     if (dkta)
-        hipMemcpy2DAsync(dkta + m0, sizeof(double) * (size_t)M, dG, sizeof(double) * (size_t)mc_max, sizeof(double) * (size_t)mc, (size_t)D * P,
-                         hipMemcpyDeviceToHost, s);
+        copy2d_to_host(dkta + m0, M, dG, mc_max, mc, (int64_t)D * P, s);
     if (dvar)
-        hipMemcpy2DAsync(dvar + m0, sizeof(double) * (size_t)M, dG + (int64_t)mc_max * D * (P - cbeg), sizeof(double) * (size_t)mc_max,
-                         sizeof(double) * (size_t)mc, (size_t)D, hipMemcpyDeviceToHost, s);
+        copy2d_to_host(dvar + m0, M, dG + (int64_t)mc_max * D * (P - cbeg), mc_max, mc, D, s);
 }
 // scratch of qg_columns behind the chunk buffers, in doubles: the partials, then the folded columns
 static void qg_extra(const gpe_ctx* c, int nseg, int64_t ldq, int64_t mc_max, size_t* n_part, size_t* n_g)

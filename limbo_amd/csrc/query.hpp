@@ -63,23 +63,13 @@ static void qt_carve(QtBufs& b, double* base)
 // grow gpe_ctx::dQuery to `bytes` (contents are not kept)
 static int query_reserve(gpe_ctx* c, size_t bytes)
 {
-    if (bytes > c->query_bytes) {
-        if (c->dQuery)
-            hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dQuery, bytes));
-        c->query_bytes = bytes;
-    }
+    HIPCHK(c, c->dQuery.reserve((bytes + sizeof(double) - 1) / sizeof(double)));
     return GPE_OK;
 }
 static void query_release(gpe_ctx* c)
 {
-    if (c->query_bytes > ((size_t)64 << 20)) { // a large batch: give the memory back
-        hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-    }
+    if (sizeof(double) * c->dQuery.capacity() > ((size_t)64 << 20)) // a large batch: give the memory back
+        c->dQuery.reset();
 }
 // X_p of every panel, compact (in front of the first chunk whose Zt is wanted)
 static void qt_panels(gpe_ctx* c, const QtBufs& b)
@@ -250,13 +240,10 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
     const size_t n_qrm = (size_t)(mc_max * std::max(D, 1)), n_qt = (size_t)(ldq * std::max(xt_rows(D), 1));
     const size_t n_ks = (size_t)(ld * mc_max), n_z = few ? n_ks : 0, n_kta = (size_t)(mc_max * P);
     const size_t need = sizeof(double) * (n_qrm + n_qt + n_ks + n_z + n_kta + 2 * (size_t)mc_max);
-    if (need > c->query_bytes) {
-        if (c->dQuery)
-            hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->dQuery, need));
-        c->query_bytes = need;
+    {
+        const int e = query_reserve(c, need);
+        if (e)
+            return e;
     }
     double* dQrm = c->dQuery;
     double* dQt = dQrm + n_qrm;
@@ -276,8 +263,7 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
             launch_build_Ks(s, c->dXt, ld, N, dQt, ldq, mc, c->kp, dKs, ld); // gp.hpp:626-632
         }
         else {
-            hipMemcpy2DAsync(dKs, sizeof(double) * ld, KsHost + m0 * N, sizeof(double) * N, sizeof(double) * N, mc,
-                             hipMemcpyHostToDevice, s);
+            copy2d_from_host(dKs, ld, KsHost + m0 * N, N, N, mc, s);
         }
         if (kta) {
             PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
@@ -319,10 +305,6 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
         }
     }
     drain_phases(c);
-    if (c->query_bytes > ((size_t)64 << 20)) { // a large batch: give the memory back
-        hipFree(c->dQuery);
-        c->dQuery = nullptr;
-        c->query_bytes = 0;
-    }
+    query_release(c);
     return rc;
 }

@@ -108,12 +108,11 @@ static bool reserve_tail(gpe_ctx* c, const TailPlan& pl, hipStream_t s, const gp
     if (!c->dTail || c->tail_cap != want_tail || c->tall_cap != want_tall) {
         if (c->dTail) {
             hipStreamSynchronize(c->stream); // (an earlier launch of this handle may still be reading the old one)
-            hipFree(c->dTail);
+            c->dTail.reset();
         }
-        c->dTail = nullptr;
         c->tail_cap = c->tall_cap = 0;
         const size_t bytes = sizeof(double) * 2 * (size_t)(want_tail + want_tall);
-        if (hipMalloc(&c->dTail, bytes) != hipSuccess)
+        if (c->dTail.reserve(2 * (size_t)(want_tail + want_tall)) != hipSuccess)
             return false;
         hipMemsetAsync(c->dTail, 0xFF, bytes, s);
         c->tail_cap = want_tail;

@@ -9,6 +9,7 @@
 //   sc : "K is given" (as joint_scratch's): A is accumulated into its dKhost, r into its obs_mean; its compute leaves Lm, in the
 //        right-hand-side rows under the factor bet^T = (Lm^-1 r)^T, and sum log diag(Lm) among the log-likelihood terms.
 struct gpe_sp_ctx {
+    DEVBUF_LOCAL ~gpe_sp_ctx() = default;
     int device = 0;
     gpe_ctx* in = nullptr;
     gpe_ctx* sc = nullptr;
@@ -18,15 +19,13 @@ struct gpe_sp_ctx {
     bool have_data = false, have_pseudo = false, have_hp = false, computed = false, prof = false;
     std::vector<double> log_b;
     double log_c = 0, log_sig = 0, jitter = 0, c = 0, sig = 0;
-    double *dX = nullptr, *dY = nullptr, *dEp = nullptr; // N x D row-major, N x P (ld N), N
-    double *dW = nullptr, *dPart = nullptr, *dBet = nullptr, *dXp2 = nullptr, *dSums = nullptr;
-    int64_t* dPlan = nullptr;
-    int64_t w_cap = 0, part_cap = 0, plan_cap = 0, xp2_cap = 0;
+    DevBuf<double> dX, dY, dEp; // N x D row-major, N x P (ld N), N
+    DevBuf<double> dW, dPart, dBet, dXp2, dSums;
+    DevBuf<int64_t> dPlan;
     std::vector<double> bet;  // M x P, host copy
     std::vector<double> nlml; // P
     double ms[5] = {0, 0, 0, 0, 0};
-    double* dGrad = nullptr; // the gradient's device block (sparse_grad.hpp)
-    int64_t grad_cap = 0;
+    DevBuf<double> dGrad; // the gradient's device block (sparse_grad.hpp)
     double gms[5] = {0, 0, 0, 0, 0};
     std::string err;
 };
@@ -47,19 +46,6 @@ int64_t sp_chunk(int64_t M, int64_t N)
             ch = round_up((int64_t)v, 64);
     }
     return std::min<int64_t>(ch, round_up(N, 64));
-}
-
-template <class T> int sp_grow(gpe_sp_ctx* h, T** p, int64_t* cap, int64_t need)
-{
-    if (need <= *cap && *p)
-        return GPE_OK;
-    if (*p)
-        hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIPCHK(h, hipMalloc(p, sizeof(T) * (size_t)need));
-    *cap = need;
-    return GPE_OK;
 }
 
 // Which Gram path: GPE_SPARSE_GRAM=1 the split-k kernel (sparse.hip), =0 the composed one (a weighted copy of V through the general
@@ -156,29 +142,11 @@ const double* sp_v_chunk(gpe_sp_ctx* h, const QtBufs& b, bool transposed, const 
 // (re)shape the scratch context for order M and P right-hand sides
 int sp_scratch(gpe_sp_ctx* h)
 {
-    gpe_ctx* sc = h->sc;
-    const int64_t M = h->M;
-    if (M > sc->cap || h->P != sc->P || !sc->dA || !sc->dKhost) {
-        if (sc->dKhost) {
-            hipFree(sc->dKhost);
-            sc->dKhost = nullptr;
-        }
-        if (alloc_dev(sc, M, 1, h->P) != GPE_OK) {
-            h->err = "sparse GP: " + sc->err;
-            return GPE_ERR_NOMEM;
-        }
-        if (hipMalloc(&sc->dKhost, sizeof(double) * (size_t)(sc->ld * sc->cap)) != hipSuccess) {
-            h->err = "sparse GP: no memory for the Gram matrix";
-            return GPE_ERR_NOMEM;
-        }
-        sc->D = 1;
-        sc->P = h->P;
+    bool fresh = false;
+    if (scratch_with_K(h->sc, h->M, h->P, &fresh) != GPE_OK) {
+        h->err = "sparse GP: " + h->sc->err;
+        return GPE_ERR_NOMEM;
     }
-    sc->N = M;
-    sc->kind = GPE_KERNEL_HOST_K;
-    sc->host_K = true;
-    sc->have_L = sc->inv_ok = sc->ll_ok = false;
-    sc->prof = false;
     return GPE_OK;
 }
 
@@ -238,18 +206,12 @@ int sp_compute_locked(gpe_sp_ctx* h)
         const int64_t rows = sparse_gram_plan(M, N, chunk, cus, nullptr, 0);
         plan.resize((size_t)rows * 5);
         (void)sparse_gram_plan(M, N, chunk, cus, plan.data(), rows);
-        int e = sp_grow(h, &h->dPlan, &h->plan_cap, rows * 5);
-        if (!e && S0 > 1)
-            e = sp_grow(h, &h->dPart, &h->part_cap, (int64_t)S0 * pstride);
-        if (e)
-            return e;
+        HIPCHK(h, h->dPlan.reserve((size_t)(rows * 5)));
+        if (S0 > 1)
+            HIPCHK(h, h->dPart.reserve((size_t)(S0 * pstride)));
         HIPCHK(h, hipMemcpyAsync(h->dPlan, plan.data(), sizeof(int64_t) * plan.size(), hipMemcpyHostToDevice, s));
     }
-    {
-        const int e = sp_grow(h, &h->dW, &h->w_cap, chunk);
-        if (e)
-            return e;
-    }
+    HIPCHK(h, h->dW.reserve((size_t)chunk));
     double* dA = sc->dKhost;
     const int64_t lda = sc->ld;
     HIPCHK(h, hipMemsetAsync(sc->dOm, 0, sizeof(double) * (size_t)(sc->ld * P), s)); // r
@@ -351,8 +313,7 @@ int sp_compute_locked(gpe_sp_ctx* h)
     // bet^T sits in the right-hand-side rows under Lm; column form for the predictions, a host copy for the likelihood
     launch_rows_to_cols(sc->stream, sc->dA + M, sc->ld, M, P, h->dBet, Mpad);
     h->bet.assign((size_t)(M * P), 0.0);
-    HIPCHK(h, hipMemcpy2DAsync(h->bet.data(), sizeof(double) * (size_t)M, h->dBet, sizeof(double) * (size_t)Mpad, sizeof(double) * (size_t)M,
-                               (size_t)P, hipMemcpyDeviceToHost, sc->stream));
+    HIPCHK(h, copy2d_to_host(h->bet.data(), M, h->dBet, Mpad, M, P, sc->stream));
     HIPCHK(h, hipStreamSynchronize(sc->stream));
     h->nlml.assign((size_t)P, 0.0);
     for (int p = 0; p < P; ++p) { // spgp.hpp:491, with the real (n - m) / 2
@@ -404,9 +365,7 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     if (transposed) {
         qt_panels(in, b);
         const int64_t npan = (M + sc->nbo - 1) / sc->nbo;
-        const int e = sp_grow(h, &h->dXp2, &h->xp2_cap, npan * sc->nbo * sc->nbo);
-        if (e)
-            return e;
+        HIPCHK(h, h->dXp2.reserve((size_t)(npan * sc->nbo * sc->nbo)));
         launch_inv_panels(s, sc->dA, sc->ld, M, (int)sc->nbo, sc->dXinv, h->dXp2, 0, nullptr, 0);
     }
     int rc = GPE_OK;
@@ -501,13 +460,9 @@ int gpe_sp_destroy(gpe_sp_handle h)
     SpDevGuard g(h);
     hipStreamSynchronize(h->in->stream);
     hipStreamSynchronize(h->sc->stream);
-    void* ps[] = {h->dX, h->dY, h->dEp, h->dW, h->dPart, h->dBet, h->dXp2, h->dSums, h->dPlan, h->dGrad};
-    for (void* p : ps)
-        if (p)
-            hipFree(p);
     gpe_destroy(h->in);
     gpe_destroy(h->sc);
-    delete h;
+    delete h; // (frees the model's own buffers: both streams are idle)
     return GPE_OK;
 }
 
@@ -523,21 +478,16 @@ int gpe_sp_set_data(gpe_sp_handle h, const double* X, int64_t N, int D, const do
     if (D != h->D)
         h->have_pseudo = h->have_hp = false; // (both are shaped by D)
     h->have_data = false;
-    for (double** p : {&h->dX, &h->dY, &h->dEp, &h->dSums}) {
-        if (*p)
-            hipFree(*p);
-        *p = nullptr;
-    }
-    HIPCHK(h, hipMalloc(&h->dX, sizeof(double) * (size_t)(N * D)));
-    HIPCHK(h, hipMalloc(&h->dY, sizeof(double) * (size_t)(N * P)));
-    HIPCHK(h, hipMalloc(&h->dEp, sizeof(double) * (size_t)N));
-    HIPCHK(h, hipMalloc(&h->dSums, sizeof(double) * (size_t)(P + 1)));
+    for (DevBuf<double>* b : {&h->dX, &h->dY, &h->dEp, &h->dSums}) // sized by the data exactly: a smaller set gives memory back
+        b->reset();
+    HIPCHK(h, h->dX.reserve((size_t)(N * D)));
+    HIPCHK(h, h->dY.reserve((size_t)(N * P)));
+    HIPCHK(h, h->dEp.reserve((size_t)N));
+    HIPCHK(h, h->dSums.reserve((size_t)(P + 1)));
     HIPCHK(h, hipMemcpy(h->dX, X, sizeof(double) * (size_t)(N * D), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(h->dY, obs_zm, sizeof(double) * (size_t)(N * P), hipMemcpyHostToDevice));
-    if (P != h->P && h->dBet) {
-        hipFree(h->dBet);
-        h->dBet = nullptr;
-    }
+    if (P != h->P)
+        h->dBet.reset();
     h->N = N;
     h->D = D;
     h->P = P;
@@ -563,12 +513,10 @@ int gpe_sp_set_pseudo(gpe_sp_handle h, const double* Xb, int64_t M)
         h->err = "sparse GP: pseudo-input model: " + h->in->err;
         return rc;
     }
-    if (h->dBet)
-        hipFree(h->dBet);
-    h->dBet = nullptr;
+    h->dBet.reset();
     h->M = M;
     h->Mpad = round_up(M, 64);
-    HIPCHK(h, hipMalloc(&h->dBet, sizeof(double) * (size_t)(h->Mpad * h->P)));
+    HIPCHK(h, h->dBet.reserve((size_t)(h->Mpad * h->P)));
     h->have_pseudo = true;
     return GPE_OK;
 }
@@ -600,7 +548,7 @@ int gpe_sp_compute(gpe_sp_handle h)
     SpDevGuard g(h);
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->have_data && h->have_pseudo && h->P > 0 && !h->dBet) // (set_data with another P after set_pseudo)
-        HIPCHK(h, hipMalloc(&h->dBet, sizeof(double) * (size_t)(h->Mpad * h->P)));
+        HIPCHK(h, h->dBet.reserve((size_t)(h->Mpad * h->P)));
     return sp_compute_locked(h);
 }
 

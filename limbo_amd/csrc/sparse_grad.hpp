@@ -98,11 +98,7 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
     const bool own_gram = sp_use_gram_kernel(M, cus);
     const int SR0 = sparse_grad_row_slices(M, std::min(chunk, N), cus); // (the first chunk is the longest)
     SpGradBufs b = sp_grad_carve(nullptr, M, N, D, P, chunk, SR0);
-    {
-        const int e = sp_grow(h, &h->dGrad, &h->grad_cap, (int64_t)b.doubles);
-        if (e)
-            return e;
-    }
+    HIPCHK(h, h->dGrad.reserve((size_t)b.doubles));
     b = sp_grad_carve(h->dGrad, M, N, D, P, chunk, SR0);
     const int64_t Mq = b.Mq, ldq = b.ldq, pstride = Mpad * Mpad;
     const int SG0 = sparse_gram_slices(M, std::min(chunk, N), cus);
@@ -111,11 +107,9 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
         const int64_t rows = sparse_gram_plan(M, N, chunk, cus, nullptr, 0);
         plan.resize((size_t)rows * 5);
         (void)sparse_gram_plan(M, N, chunk, cus, plan.data(), rows);
-        int e = sp_grow(h, &h->dPlan, &h->plan_cap, rows * 5);
-        if (!e && SG0 > 1)
-            e = sp_grow(h, &h->dPart, &h->part_cap, (int64_t)SG0 * pstride);
-        if (e)
-            return e;
+        HIPCHK(h, h->dPlan.reserve((size_t)(rows * 5)));
+        if (SG0 > 1)
+            HIPCHK(h, h->dPart.reserve((size_t)(SG0 * pstride)));
         HIPCHK(h, hipMemcpyAsync(h->dPlan, plan.data(), sizeof(int64_t) * plan.size(), hipMemcpyHostToDevice, s));
     }
     std::vector<hipEvent_t> ev[5];

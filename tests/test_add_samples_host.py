@@ -17,7 +17,7 @@ ROOT = Path(__file__).resolve().parent.parent
 DRIVER = ROOT / "tests" / "cpp" / "test_add_samples"
 # gpe.h's declared entry points as this change found them (tests/test_abi.py holds the oracle to the C-ABI among them)
 GPE_H_SYMBOLS = """gpe_add_sample gpe_batch_compute gpe_batch_hp_objective gpe_batch_log_lik gpe_clone gpe_clone_to gpe_compute
-gpe_compute_inv_kernel gpe_create gpe_debug_chain_split gpe_debug_inv_plan gpe_debug_ragged_split gpe_debug_tail_order
+gpe_compute_inv_kernel gpe_create gpe_debug_chain_split gpe_debug_inv_plan gpe_debug_live_buffers gpe_debug_ragged_split gpe_debug_tail_order
 gpe_debug_tail_plan gpe_debug_tri_tile_map gpe_destroy gpe_device_count gpe_epoch gpe_flow_retries gpe_get_K gpe_get_Kinv gpe_get_L
 gpe_get_alpha gpe_get_device gpe_get_loo_weights gpe_get_phase_ms gpe_get_stream gpe_handover_reruns gpe_hbm_stream_peak
 gpe_hp_objective gpe_last_error gpe_log_lik gpe_log_lik_grad gpe_log_loo_cv gpe_log_loo_cv_grad gpe_mfma_f64_peak gpe_nb_samples

@@ -734,6 +734,91 @@ def test_gpu_data_flow_buffers_across_sizes_on_one_handle(engine_lib):
     h.close()
 
 
+def _life_cycle_tool():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("schedule_identity", ROOT / "tools" / "schedule_identity.py")
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+def test_gpu_handle_life_cycle_vs_oracle_and_live_buffers(engine_lib, oracle_lib):
+    """One handle through every event that allocates, grows, drops or hands on a device buffer — the `lifecycle` case of
+    tools/schedule_identity.py: set_data at N = 300 (capacity 320), K^-1 and the LOO gradient, 30 add_sample calls across the
+    capacity, a 16 384-point query whose scratch (> 64 MiB) is given back, a change of P, a set_data beyond the capacity, a clone
+    that outlives its source — every value against the C oracle driven through the same calls (tests/parity_checks.py's bars),
+    then the owner type's count (gpe_debug_live_buffers): a second pass over the life cycle, a sparse model included, leaves the
+    count and the bytes where the first left them, and a handle holds what alloc_dev's formulas (engine.hip, restated here) say:
+    right after set_data exactly that, after compute that plus the pair of hand-over buffers of its one data-flow launch."""
+    import gc
+
+    from tests import high_dim as HD
+
+    SI = _life_cycle_tool()
+    ref = dict(SI.lifecycle_steps(np, oracle_lib, _capi.Handle, int(O.SE_ARD)))
+    live = lambda: np.array(_capi.debug_live_buffers(engine_lib))
+
+    def alloc_dev_bytes(N, D, P):  # alloc_dev, ld_for, xt_rows, max_lam (GPE_MAX_THETA = 64, blocks of 64 rows, pad 16)
+        cap = -(-max(N, 64) // 64) * 64
+        ld = cap + -(-(P + 16) // 16) * 16
+        xt_rows = D + max(0, min(D, (64 - 1 - D) // max(D, 1)))
+        return 8 * (ld * xt_rows + ld * cap + 2 * ld * P + 2 * ld * max(P, 1) + (cap // 64) * 64 * 64)
+
+    def tail_pair_bytes(N, P):  # reserve_tail: two buffers of tail_buf_doubles(nt, nb) (dev.h); no tall launch at this size
+        pl = HD.plan(N, P)
+        assert pl["t0"] == 0 and pl["e0"] == -1
+        nt, nb = pl["nt_tail"], pl["nb_tail"]
+        return 8 * 2 * (nt * 3072 + (nt * nb - nt * (nt - 1) // 2) * 4096)
+
+    def check(label, got):
+        want = ref[label]
+        what = label.split(".", 1)[1].split("_")[0]
+        if what in ("log", "lik"):
+            assert abs(got - want) <= PC.TOL_LL * max(1.0, abs(want)), label
+        elif what == "loo" and np.ndim(got) == 0:
+            assert abs(got - want) <= 1e-9 * max(1.0, abs(want)), label
+        elif what in ("loo", "grad"):
+            assert relerr_norm(got, want) < PC.TOL_GRAD, label
+        elif what in ("Kinv", "alpha"):
+            assert relerr_norm(got, want) < 1e-9, label
+        elif what == "kta":  # mu = kta + m(v), the mean of the centred observations being 0 (synth.finish_query)
+            assert relerr(got, want, floor=1e-3) < PC.TOL_MU, label
+        else:
+            assert what == "var", label
+            assert relerr(synth.finish_query(0.0, got, 0.0, SI.NOISE)[1], synth.finish_query(0.0, want, 0.0, SI.NOISE)[1]) < PC.TOL_VAR, label
+
+    def one_pass():
+        before = live()
+        seen = 0
+        for label, got in SI.lifecycle_steps(np, engine_lib, _capi.Handle, int(O.SE_ARD)):
+            if label == "1.set_data":
+                assert tuple(live() - before) == (7, alloc_dev_bytes(300, SI.D, 2))
+            elif label == "1.log_lik":  # after compute only
+                assert tuple(live() - before) == (8, alloc_dev_bytes(300, SI.D, 2) + tail_pair_bytes(300, 2))
+            if got is not None:
+                check(label, got)
+                seen += 1
+        assert seen == len(ref) - 1 == 19
+        rng = np.random.default_rng(2003)
+        X = rng.uniform(-2.0, 2.0, (500, SI.D))
+        sp = _capi.SparseHandle(engine_lib)
+        sp.set_data(X, np.sin(X.sum(axis=1))[:, None])
+        sp.set_pseudo(X[:64])
+        sp.set_hparams(np.zeros(SI.D), 0.0, np.log(0.01), 1e-6)
+        assert sp.compute() == 0
+        sp.close()
+
+    gc.collect()  # (handles other tests left to the collector go now, not between two readings)
+    first = live()
+    one_pass()  # warms the pool of streams and pinned blocks that destroyed handles leave behind
+    second = live()
+    one_pass()
+    third = live()
+    assert tuple(third) == tuple(second), (first, second, third)
+    assert tuple(second) == tuple(first), (first, second, third)  # every handle of a pass is destroyed: nothing of it is left
+
+
 def test_gpu_cached_first_look_never_sees_a_stale_slot(engine_lib):
     """the first look at a polled hand-over slot is a cacheable (workgroup-scope) load, only the re-reads are device-scope (potrf_tile.h: PolledTile):
     sound as long as every kernel boundary writes back / invalidates the L2 lines of the slots, so that a word which is not

@@ -10,6 +10,9 @@ child process with its own environment (the switches are read once per process),
 limit; the first child that fails ends the run.  A case calls compute() twice on one handle and prints one JSON line:
 the (stream index, kernel, grid, block) sequence of the SECOND evaluation (gpe_trace / gpe_trace_dump), the sha256 of
 tril(get_L()) and of get_alpha(), and the bits of log_lik().  D = 4, SE-ARD, noise 0.01.
+
+The case `lifecycle` is about the handle's memory instead of the schedule: one handle through every event that allocates, grows,
+drops or hands on a device buffer (lifecycle_steps); it prints the sha256 of every array returned and the bits of every scalar.
 """
 import argparse
 import hashlib
@@ -49,6 +52,7 @@ CASES = {
     "v": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_FUSE_DIAG": "0", "GPE_STOP_EVENT": "0"}, "the marker-packet form in the panels"),
     "w": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_LOOKAHEAD": "0"}, "single stream in the panels"),
 }
+CASES["lifecycle"] = (300, 2, {}, "one handle through set_data, grow, the query scratch's give-back, a change of P, clone and destroy")
 D = 4
 NOISE = 0.01
 CHILD_TIMEOUT_S = 180
@@ -62,6 +66,75 @@ def problem(np, N, P, seed):
     return X, Y - Y.mean(axis=0)
 
 
+def lifecycle_steps(np, lib, Handle, se_ard):
+    """One handle (of `lib`: the engine, or the oracle behind the same binding) through the events that move device memory, in
+    order; yields (label, array or scalar) for everything a call returns.  The consumer may look at the process between two
+    steps (tests/test_gpu_configs.py reads the live-buffer count there)."""
+    theta = 0.1 * np.arange(D + 1) - 0.2
+    X, Y = problem(np, 330, 2, 2000)
+    h = Handle(lib, 0)
+    # 1. N = 300 in a capacity of 320; K^-1, the LOO value and its gradient (dLinv, dKinv, dInvS.., dLooS, dLooV, dGradPartial)
+    h.set_data(X[:300], Y[:300])
+    h.set_kernel(se_ard, theta, NOISE)
+    yield "1.set_data", None
+    assert h.compute() == 0
+    yield "1.log_lik", h.log_lik()
+    yield "1.Kinv", h.get_Kinv()
+    yield "1.loo", h.log_loo_cv()
+    yield "1.loo_grad", h.log_loo_cv_grad(False)
+    # 2. 30 samples one by one: 321 crosses the capacity (a multiple of the 64-row block) and takes the grow
+    for n in range(300, 330):
+        assert h.add_sample(X[n], Y[: n + 1]) == 0
+    yield "2.alpha", h.get_alpha()
+    yield "2.log_lik", h.log_lik()
+    # 3. what the grow dropped, again
+    yield "3.Kinv", h.get_Kinv()
+    yield "3.loo_grad", h.log_loo_cv_grad(False)
+    # 4. a batch whose scratch exceeds 64 MiB (given back), then a handful of points (allocated again, small)
+    Xq = np.random.default_rng(2001).uniform(-2.0, 2.0, (16384, D))
+    kta, var = h.query_batch(Xq)
+    yield "4.kta_16384", kta
+    yield "4.var_16384", var
+    kta, var = h.query_batch(Xq[:3])
+    yield "4.kta_3", kta
+    yield "4.var_3", var
+    # 5. fewer samples but another P: everything anew
+    X1, Y1 = problem(np, 700, 1, 2002)
+    h.set_data(X1[:200], Y1[:200])
+    assert h.compute() == 0
+    yield "5.alpha", h.get_alpha()
+    yield "5.log_lik", h.log_lik()
+    # 6. more samples than the capacity
+    h.set_data(X1, Y1)
+    lik, grad, rc = h.hp_objective(se_ard, theta + 0.05, NOISE, False, True)
+    assert rc == 0
+    yield "6.lik", lik
+    yield "6.grad", grad
+    # 7. the clone outlives its source
+    c = h.clone()
+    h.close()
+    assert c.compute() == 0
+    yield "7.alpha", c.get_alpha()
+    kta, var = c.query_batch(Xq[:1000])
+    yield "7.kta", kta
+    yield "7.var", var
+    c.close()
+
+
+def run_lifecycle(np, _capi):
+    import numbers
+
+    out = {"case": "lifecycle"}
+    for label, v in lifecycle_steps(np, _capi.load_engine(), _capi.Handle, _capi.KERNEL_SE_ARD):
+        if v is None:
+            continue
+        if isinstance(v, numbers.Real):
+            out[label + "_bits"] = struct.pack(">d", v).hex()
+        else:
+            out[label + "_sha256"] = hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()
+    print(json.dumps(out), flush=True)
+
+
 def run_case(name, root):
     sys.path.insert(0, str(root))
     import numpy as np
@@ -69,6 +142,8 @@ def run_case(name, root):
     from limbo_amd import _capi
 
     assert Path(_capi.__file__).resolve().is_relative_to(root), _capi.__file__
+    if name == "lifecycle":
+        return run_lifecycle(np, _capi)
     N, P, _, _ = CASES[name]
     lib = _capi.load_engine()
     hs = []
