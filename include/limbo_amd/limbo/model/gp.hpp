@@ -55,6 +55,7 @@
 #include <limbo/mean/data.hpp>
 #include <limbo/model/gp/host_small.hpp>
 #include <limbo/model/gp/query_grad.hpp>
+#include <limbo/model/gp/pathwise.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -448,6 +449,57 @@ namespace limbo {
                 argmax.assign((size_t)(n_draws * _dim_out), 0);
                 fmax.assign((size_t)(n_draws * _dim_out), 0.0);
                 _draws(points, Z, n_draws, jitter, nullptr, argmax.data(), fmax.data());
+            }
+
+            /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise
+            /// conditioning on n_features random Fourier features.  The set is evaluated anywhere, any number of times, with its
+            /// exact gradient in the point; one multi-right-hand-side solve here, no solve per point later, no cap on the points.
+            /// Omega0 (n_features x Dw, row-major), phase (n_features), W (n_features x n_draws x dim_out) and E (samples x n_draws x
+            /// dim_out; empty: zeros) in the layouts of gpe_pathwise.h: a deterministic function of (model, Omega0, phase, W, E).
+            /// On the model's home device; a host-resident model (and a model without samples: the prior's paths, Phi w + m): on
+            /// the host from matrixL() and limbo_amd::query_grad::dk_dv; kernels without device code: std::logic_error.
+            using PathSet = limbo_amd::pathwise::PathSet;
+            PathSet sample_paths(int n_features, int n_draws, const std::vector<double>& Omega0, const std::vector<double>& phase,
+                const std::vector<double>& W, const std::vector<double>& E) const
+            {
+                constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
+                if (kind == limbo_amd::KIND_HOST_K)
+                    throw std::logic_error("limbo_amd: sample_paths(): this kernel has no device code, hence no spectral law and no derivative in the query point");
+                const int64_t n = _samples.size();
+                const int D = _dim_in, P = _dim_out, R = n_features, S = n_draws;
+                const Eigen::VectorXd hp = _kernel_function.h_params();
+                const int nk = (int)hp.size() - (Params::kernel::optimize_noise() ? 1 : 0);
+                const int Dw = limbo_amd::pathwise::freq_dim(kind, nk, D);
+                if (R < 1 || S < 1 || (int64_t)Omega0.size() < (int64_t)R * Dw || (int64_t)phase.size() < R || (int64_t)W.size() < (int64_t)R * S * P
+                    || (!E.empty() && (int64_t)E.size() < n * S * P))
+                    throw std::runtime_error("limbo_amd: sample_paths(): Omega0, phase, W or E is smaller than features x draws x dim_out asks for");
+                auto mean = [this](const Eigen::VectorXd& v) { return Eigen::VectorXd(_mean_function(v, *this)); };
+                if (n == 0 || _host_mode) {
+                    std::vector<double> X((size_t)(n * D));
+                    for (int64_t i = 0; i < n; ++i)
+                        for (int d = 0; d < D; ++d)
+                            X[(size_t)(i * D + d)] = _samples[(size_t)i](d);
+                    limbo_amd::pathwise::HostPaths h;
+                    h.make(kind, hp.data(), nk, D, P, X.data(), n, n ? matrixL().data() : nullptr, _obs_mean.data(), _kernel_function.noise(), R, S,
+                        Omega0.data(), phase.data(), W.data(), E.empty() ? nullptr : E.data());
+                    return PathSet(std::move(h), mean);
+                }
+                gpe_paths ps = nullptr;
+                _eng.check(gpe_paths_create(_eng.get(), R, S, Omega0.data(), phase.data(), W.data(), E.empty() ? nullptr : E.data(), &ps), "gpe_paths_create");
+                return PathSet(ps, D, P, S, mean);
+            }
+            /// ... with everything from the seed: limbo_amd::pathwise::spectral_draws(kind, n_features, Dw, seed), W from
+            /// standard_normals(.., seed + 1) and E from standard_normals(.., seed + 2)
+            PathSet sample_paths(int n_features, int n_draws, uint64_t seed) const
+            {
+                constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
+                if (kind == limbo_amd::KIND_HOST_K)
+                    throw std::logic_error("limbo_amd: sample_paths(): this kernel has no device code, hence no spectral law and no derivative in the query point");
+                const int nk = (int)_kernel_function.h_params().size() - (Params::kernel::optimize_noise() ? 1 : 0);
+                const limbo_amd::pathwise::Spectral sp = limbo_amd::pathwise::spectral_draws(kind, n_features, limbo_amd::pathwise::freq_dim(kind, nk, _dim_in), seed);
+                const size_t cols = (size_t)std::max(n_draws, 0) * (size_t)_dim_out;
+                return sample_paths(n_features, n_draws, sp.Omega0, sp.phase, standard_normals((size_t)std::max(n_features, 0) * cols, seed + 1),
+                    standard_normals(_samples.size() * cols, seed + 2));
             }
 
             int dim_in() const

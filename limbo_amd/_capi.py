@@ -135,6 +135,13 @@ def _sig(lib, prefix):
             # include/gpe_query_grad.h: the batched posterior with its gradient in the query point
             "query_batch_grad": [_vp, _dp, _i64, _dp, _dp, _dp, _dp],
             "query_grad_phase_ms": [_vp, _dp],
+            # include/gpe_pathwise.h: posterior draws as functions of the query point
+            "paths_create": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(_vp)],
+            "paths_eval": [_vp, _dp, _i64, _dp, _dp, _dp],
+            "paths_argmax": [_vp, _dp, _i64, _dp, C.POINTER(_i64), _dp],
+            "paths_info": [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+            "paths_phase_ms": [_vp, _dp],
+            "paths_destroy": [_vp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -444,6 +451,12 @@ class Handle:
         self._chk(self.lib.fn("query_grad_phase_ms")(self._h, _d(ms)), "query_grad_phase_ms")
         return dict(zip(("forward", "backward", "grad"), ms.tolist()))
 
+    # -- posterior draws as functions of the query point (include/gpe_pathwise.h; HIP library only)
+    def paths(self, R, S, Omega0, phase, W, E=None) -> "Paths":
+        """A set of S pathwise draws per output on R Fourier features.  Omega0: (R, Dw) unit-scale frequencies, phase: (R),
+        W: (R, S, P) and E: (N, S, P) standard normals (E = None: zeros)."""
+        return Paths(self, R, S, Omega0, phase, W, E)
+
     # -- accessors
     def nb_samples(self) -> int:
         n = _i64()
@@ -503,6 +516,72 @@ class Handle:
         self._chk(self.lib.fn("get_phase_ms")(self._h, _d(ms), ln, _d(fl), PH_COUNT), "get_phase_ms")
         return {PHASE_NAMES[i]: {"ms": float(ms[i]), "launches": int(ln[i]), "flops": float(fl[i])}
                 for i in range(PH_COUNT)}
+
+
+class Paths:
+    """A path set behind include/gpe_pathwise.h: a snapshot of the model it was made from, independent of the handle afterwards."""
+
+    def __init__(self, handle: Handle, R, S, Omega0, phase, W, E=None):
+        self.lib = handle.lib
+        P = handle.P
+        Om = _c(Omega0).reshape(R, -1)
+        ph = _c(phase).reshape(R)
+        Wf = _c(np.asarray(W, dtype=np.float64).reshape(R, S * P, order="F"), "F")
+        Ef = None if E is None else _c(np.asarray(E, dtype=np.float64).reshape(-1, S * P, order="F"), "F")
+        ps = _vp()
+        rc = self.lib.fn("paths_create")(handle._h, int(R), int(S), _d(Om), _d(ph), _d(Wf), _d(Ef) if Ef is not None else None, C.byref(ps))
+        self._ps = None
+        handle._chk(rc, "paths_create")
+        self._ps = ps
+        n, d, p, r, s = _i64(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.lib.fn("paths_info")(ps, C.byref(n), C.byref(d), C.byref(p), C.byref(r), C.byref(s)), "paths_info")
+        self.N, self.D, self.P, self.R, self.S = n.value, d.value, p.value, r.value, s.value
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise EngineError(f"gpe_{what} failed: status {rc}")
+        return rc
+
+    def close(self):
+        if getattr(self, "_ps", None):
+            self.lib.fn("paths_destroy")(self._ps)
+            self._ps = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _points(self, V, mean_q):
+        V = _c(V).reshape(-1, self.D)
+        mq = None if mean_q is None else _c(np.asarray(mean_q, dtype=np.float64).reshape(V.shape[0], self.P), "F")
+        return V, mq
+
+    def eval(self, V, want=("F", "dF"), mean_q=None):
+        """(F (T, S, P), dF (T, D, S, P)), None for what `want` leaves out: dF[t, d, s, p] = d f_sp / d x_d at point t (without the
+        mean functor's derivative); mean_q (T, P): m(v), added to F."""
+        V, mq = self._points(V, mean_q)
+        T, D, S, P = V.shape[0], self.D, self.S, self.P
+        F = np.zeros((T, S * P), order="F") if "F" in want else None
+        dF = np.zeros((T, D * S * P), order="F") if "dF" in want else None
+        self._chk(self.lib.fn("paths_eval")(self._ps, _d(V), T, _d(mq) if mq is not None else None, _d(F) if F is not None else None,
+                                            _d(dF) if dF is not None else None), "paths_eval")
+        return (F.reshape(T, S, P, order="F") if F is not None else None, dF.reshape(T, D, S, P, order="F") if dF is not None else None)
+
+    def argmax(self, V, mean_q=None):
+        """(argmax (S, P), fmax (S, P)) of every draw over the points; the lowest index on exact ties"""
+        V, mq = self._points(V, mean_q)
+        am, fm = np.zeros(self.S * self.P, dtype=np.int64), np.zeros(self.S * self.P)
+        self._chk(self.lib.fn("paths_argmax")(self._ps, _d(V), V.shape[0], _d(mq) if mq is not None else None,
+                                              am.ctypes.data_as(C.POINTER(_i64)), _d(fm)), "paths_argmax")
+        return am.reshape(self.S, self.P, order="F"), fm.reshape(self.S, self.P, order="F")
+
+    def phase_ms(self):
+        """{create_features, create_solve, eval_features, eval_data} in ms"""
+        ms = np.zeros(4)
+        self._chk(self.lib.fn("paths_phase_ms")(self._ps, _d(ms)), "paths_phase_ms")
+        return dict(zip(("create_features", "create_solve", "eval_features", "eval_data"), ms.tolist()))
 
 
 def sparsify(lib, X, max_points, device_id=0):

@@ -496,6 +496,22 @@ void launch_draws(hipStream_t s, const double* Cm, int64_t ldc, int64_t M, const
 // out[2 col] = max of column col of F, out[2 col + 1] = the bits of the lowest index (int64) that holds it
 void launch_argmax(hipStream_t s, const double* F, int64_t M, int ncols, double* out);
 
+// ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
+// slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
+int paths_slots(bool grad, int R);
+// one pass over NB basis functions for M points: mode 0 the Fourier features (Bt = Omega0 by rows, Cf = amp W), mode 1 the data term
+// (Bt = the samples by rows, scaled: launch_paths_scale_rows; Cf = U);  part[((seg ncol + c) slots + slot) ldp + m]
+void launch_paths_basis(hipStream_t s, int mode, bool grad, const double* Qt, int64_t ldq, int64_t M, const double* Bt, int64_t ldb, int64_t NB,
+                        const double* phase, const double* Cf, int64_t ldc, int ncol, const KParams& kp, int nseg, double* part, int64_t ldp);
+void launch_paths_scale_rows(hipStream_t s, const double* src, int64_t lds, double* dst, int64_t ldd, int64_t n, const KParams& kp);
+void launch_paths_fold(hipStream_t s, const double* partF, int nsegF, const double* partK, int nsegK, int64_t ldp, int NS, int ncol, int64_t M,
+                       const KParams& kp, const LamParams& lp, const double* mean, int64_t ldm, int S, double* F, int64_t ldf, double* dF,
+                       int64_t ldo);
+void launch_paths_residual(hipStream_t s, const double* partF, int nsegF, int64_t ldp, int ncol, int64_t n, int64_t i0, const double* om,
+                           int64_t ldom, int S, int c_first, const double* E, int64_t lde, double sn, double* Rt, int64_t ldr);
+void launch_paths_untranspose(hipStream_t s, const double* Wt, int64_t ldw, int64_t n, int ncol, double* U, int64_t ldu);
+void launch_paths_argmax(hipStream_t s, const double* F, int64_t ldf, int64_t M, int ncol, int64_t t0, bool first, double* run);
+
 // ---- gradient of the batched posterior in the query point (qgrad.hip; include/gpe_query_grad.h) ------------------------
 size_t query_grad_partial_doubles(int nseg, int ncol, int R, int64_t ldp);
 // columns [cbeg, cbeg + ncol) of { alpha_0 .. alpha_{P-1}, -2 Wt } (Wt = (K^-1 k(X, V))^T, M x N, ldw; null unless column P is among

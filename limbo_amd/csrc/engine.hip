@@ -20,6 +20,7 @@
 #include "../../include/gpe_sparse.h"
 #include "../../include/gpe_sparse_grad.h"
 #include "../../include/gpe_query_grad.h"
+#include "../../include/gpe_pathwise.h"
 #include "dev.h"
 #include "devbuf.h"
 
@@ -34,6 +35,7 @@
 #include <map>
 #include <dlfcn.h>
 #include <fcntl.h>
+#include <functional>
 #include <sys/file.h>
 #include <sys/stat.h>
 #include <thread>
@@ -1263,6 +1265,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 }
 
 #include "qgrad.hpp" // the posterior's gradient in the query point over a point batch (include/gpe_query_grad.h)
+#include "pathwise.hpp" // posterior draws as functions of the query point: Fourier features + Matheron's rule (include/gpe_pathwise.h)
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
 #include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)

@@ -46,3 +46,16 @@ static __device__ __forceinline__ double kfun_fast_rt(int kind, double z, double
         return kfun_fast<1>(z, sf2);
     return kfun_fast<2>(z, sf2);
 }
+
+// d k(v, x) / d v = g(z) Mm (v - x) (include/gpe_query_grad.h): g(z) by run-time kind (gpe_kernel_kind), finite and continuous at z = 0
+static __device__ __forceinline__ double kgrad_fast_rt(int kind, double z, double sf2)
+{
+    if (kind == 0 || kind == 3)
+        return -sf2 * exp_nonpos(-0.5 * z);
+    if (kind == 1) {
+        const double t = 2.23606797749978969641 * sqrt(z);
+        return (-5.0 / 3.0) * sf2 * (1.0 + t) * exp_nonpos(-t);
+    }
+    const double t = 1.73205080756887729353 * sqrt(z);
+    return -3.0 * sf2 * exp_nonpos(-t);
+}

@@ -13,19 +13,6 @@
 
 #define QG_LANES 64 // thread = point; one wave per workgroup (LDS per workgroup is small: many workgroups per CU)
 
-// g(z) by run-time kind (gpe_kernel_kind), finite and continuous at z = 0
-static __device__ __forceinline__ double kgrad_fast_rt(int kind, double z, double sf2)
-{
-    if (kind == 0 || kind == 3)
-        return -sf2 * exp_nonpos(-0.5 * z);
-    if (kind == 1) {
-        const double t = 2.23606797749978969641 * sqrt(z);
-        return (-5.0 / 3.0) * sf2 * (1.0 + t) * exp_nonpos(-t);
-    }
-    const double t = 1.73205080756887729353 * sqrt(z);
-    return -3.0 * sf2 * exp_nonpos(-t);
-}
-
 // part[((seg ncol + c) R + r) ldp + m] = sum over the samples i of segment seg of  C_c[m, i] g(z_mi) s_r (v_mr - x_ir)
 //   grid: x = 64-point groups, y = segments of the samples (gridDim.y of them, equal lengths), z = (row tile, column tile)
 //   LDS : qs[R][64] the workgroup's points, xs[R][ch] and as[CT][ch] a stretch of ch samples (ch a multiple of 4), all scaled by s_r

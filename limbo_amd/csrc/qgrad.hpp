@@ -56,11 +56,60 @@ static void qg_extra(const gpe_ctx* c, int nseg, int64_t ldq, int64_t mc_max, si
     *n_g = (size_t)mc_max * (size_t)c->D * (size_t)(c->P + 1);
 }
 
+// the backward half behind qt_forward, for the mc rows of b.dZt (needs qt_panels)
+static void qt_backward(gpe_ctx* c, const QtBufs& b, int64_t mc)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, ld = c->ld, nbo = c->nbo, ldq = b.ldq;
+    // Wt = Zt L^-1, from the last outer panel to the first; Zt is the running right-hand side (destroyed), Wt goes where
+    // Kst was (b.dKst):
+    //   Wt[:, p]        = Acc[:, p] X_p                       X_p = inv(L_pp) (qt_panels), untransposed this time
+    //   Acc[:, 0 .. o0) -= Wt[:, p] L[p, 0 .. o0)
+    // Both products have B with k contiguous: the register-staged matrix-core kernel (the direct-to-LDS one takes
+    // operands contiguous along their non-k index only, gemm.hip: glds_ok).
+    for (int64_t o0 = (b.npan - 1) * nbo; o0 >= 0; o0 -= nbo) {
+        const int64_t pw = std::min<int64_t>(nbo, N - o0);
+        {
+            GemmArgs g{};
+            g.C = b.dKst + o0 * ldq;
+            g.ldc = ldq;
+            g.A = b.dZt + o0 * ldq;
+            g.lda = ldq;
+            g.B = b.dXp + (o0 / nbo) * (nbo * nbo);
+            g.ldb = nbo;
+            g.b_kmajor = 1;
+            g.m = mc;
+            g.n = pw;
+            g.k = pw;
+            g.overwrite = 1;
+            g.tile = b.qtile;
+            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+            launch_gemm_sub(s, g);
+        }
+        if (o0 > 0) {
+            GemmArgs g{};
+            g.tile = b.qtile;
+            g.C = b.dZt;
+            g.ldc = ldq;
+            g.A = b.dKst + o0 * ldq;
+            g.lda = ldq;
+            g.B = c->dA + o0;
+            g.ldb = ld;
+            g.b_kmajor = 1;
+            g.m = mc;
+            g.n = o0;
+            g.k = pw;
+            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+            launch_gemm_sub(s, g);
+        }
+    }
+}
+
 // The transposed layout (query_transposed's loop): Zt = Kst L^-T, var from Zt, then Wt = Zt L^-1 into the buffer Kst occupied.
 static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
 {
     hipStream_t s = c->stream;
-    const int64_t N = c->N, ld = c->ld, nbo = c->nbo;
+    const int64_t N = c->N;
     const int D = c->D;
     int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64); // (the query's rule)
     mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
@@ -92,49 +141,8 @@ static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
             hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
         mk.mark(1);
-        if (dvar) {
-            // Wt = Zt L^-1, from the last outer panel to the first; Zt is the running right-hand side, Wt goes where Kst was:
-            //   Wt[:, p]        = Acc[:, p] X_p                       X_p = inv(L_pp) (qt_panels), untransposed this time
-            //   Acc[:, 0 .. o0) -= Wt[:, p] L[p, 0 .. o0)
-            // Both products have B with k contiguous: the register-staged matrix-core kernel (the direct-to-LDS one takes
-            // operands contiguous along their non-k index only, gemm.hip: glds_ok).
-            for (int64_t o0 = (b.npan - 1) * nbo; o0 >= 0; o0 -= nbo) {
-                const int64_t pw = std::min<int64_t>(nbo, N - o0);
-                {
-                    GemmArgs g{};
-                    g.C = b.dKst + o0 * ldq;
-                    g.ldc = ldq;
-                    g.A = b.dZt + o0 * ldq;
-                    g.lda = ldq;
-                    g.B = b.dXp + (o0 / nbo) * (nbo * nbo);
-                    g.ldb = nbo;
-                    g.b_kmajor = 1;
-                    g.m = mc;
-                    g.n = pw;
-                    g.k = pw;
-                    g.overwrite = 1;
-                    g.tile = b.qtile;
-                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
-                    launch_gemm_sub(s, g);
-                }
-                if (o0 > 0) {
-                    GemmArgs g{};
-                    g.tile = b.qtile;
-                    g.C = b.dZt;
-                    g.ldc = ldq;
-                    g.A = b.dKst + o0 * ldq;
-                    g.lda = ldq;
-                    g.B = c->dA + o0;
-                    g.ldb = ld;
-                    g.b_kmajor = 1;
-                    g.m = mc;
-                    g.n = o0;
-                    g.k = pw;
-                    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
-                    launch_gemm_sub(s, g);
-                }
-            }
-        }
+        if (dvar)
+            qt_backward(c, b, mc);
         mk.mark(2);
         if (grads)
             qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? b.dKst : nullptr, ldq, b.nseg, dPartG, dG, dkta, dvar, m0, M);

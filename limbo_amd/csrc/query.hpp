@@ -77,33 +77,13 @@ static void qt_panels(gpe_ctx* c, const QtBufs& b)
     PhaseScope ps(c, GPE_PH_QUERY, 0.0);
     launch_inv_panels(c->stream, c->dA, c->ld, c->N, (int)c->nbo, c->dXinv, b.dXp, 0, nullptr, 0);
 }
-// one chunk of mc points (host, row-major): the points, Kst, kta (on the device and, kta != null, to kta[m0 + p M]) and,
-// want_z, Zt = Kst L^-T (Kst is destroyed)
-static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
-                     bool want_z)
+// Zt = Kst L^-T for the mc rows of b.dKst — a chunk's cross kernel, or right-hand sides a caller put in its place (pathwise.hpp);
+// Kst is destroyed
+static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc)
 {
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld, nbo = c->nbo, ldq = b.ldq;
-    const int D = c->D, P = c->P;
     double *dKst = b.dKst, *dZt = b.dZt;
-    hipMemcpyAsync(b.dQrm, Xq_chunk, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
-    launch_transpose_x(s, b.dQrm, mc, D, b.dQt, ldq, 0);
-    project_lambda(c, s, b.dQt, ldq, 0, mc);
-    {
-        // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
-        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-        launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldq); // gp.hpp:626-632
-    }
-    if (want_kta) {
-        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
-        launch_kta_t(s, dKst, ldq, N, mc, c->dAl, ld, P, b.dKta, b.mc_max, b.dPart, ldq, b.nseg); // gp.hpp:615
-        if (kta)
-            for (int p = 0; p < P; ++p)
-                hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc,
-                               hipMemcpyDeviceToHost, s);
-    }
-    if (!want_z)
-        return;
     for (int64_t o0 = 0; o0 < N; o0 += nbo) { // gp.hpp:620, transposed
         const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
         {
@@ -138,6 +118,35 @@ static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_
             launch_gemm_sub(s, g);
         }
     }
+}
+// one chunk of mc points (host, row-major): the points, Kst, kta (on the device and, kta != null, to kta[m0 + p M]) and,
+// want_z, Zt = Kst L^-T (Kst is destroyed)
+static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
+                     bool want_z)
+{
+    hipStream_t s = c->stream;
+    const int64_t N = c->N, ld = c->ld, ldq = b.ldq;
+    const int D = c->D, P = c->P;
+    double* dKst = b.dKst;
+    hipMemcpyAsync(b.dQrm, Xq_chunk, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
+    launch_transpose_x(s, b.dQrm, mc, D, b.dQt, ldq, 0);
+    project_lambda(c, s, b.dQt, ldq, 0, mc);
+    {
+        // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
+        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+        launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldq); // gp.hpp:626-632
+    }
+    if (want_kta) {
+        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
+        launch_kta_t(s, dKst, ldq, N, mc, c->dAl, ld, P, b.dKta, b.mc_max, b.dPart, ldq, b.nseg); // gp.hpp:615
+        if (kta)
+            for (int p = 0; p < P; ++p)
+                hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc,
+                               hipMemcpyDeviceToHost, s);
+    }
+    if (!want_z)
+        return;
+    qt_forward(c, b, mc);
 }
 
 static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var)
