@@ -106,11 +106,10 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
     // Point by point — gpe_add_sample's launches AND its host wait per point (one launch and a spin on a pinned word on the small
     // path, the three sweeps and a stream wait above it) — while the model has less than one outer panel (the transposed solve
     // needs one), when the whole append stays inside the one-launch small path, and for a panel width that layout does not serve
-    const bool block_ok = c->nbo % 128 == 0 && c->nbo <= 256;
     const bool small_all = c->small_path && nfin <= small_max_n() && P <= 3;
     int status = 0;
     int64_t done = 0;
-    while (done < q && (c->N < c->nbo || small_all || !block_ok)) {
+    while (done < q && (small_all || !qt_serves(c))) {
         const int rc = add_sample_locked(c, X + done * D, D, obs_mean, nfin, P, n0 == 0 && done == 0);
         if (rc < 0)
             return rc;
@@ -129,12 +128,9 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
     // 65 536 samples: append_slices_cap) and the chunk buffers of the last chunk's layout, which grows with n
     const int slices_cap = append_slices_cap(nfin);
     const size_t extra = append_scratch_doubles(nfin);
-    {
-        const QtBufs bmax = qt_layout(c, append_max_chunk(), nfin, nfin);
-        const int e = query_reserve(c, sizeof(double) * (extra + bmax.doubles));
-        if (e)
-            return e;
-    }
+    QueryScratch qs(c);
+    if (const int e = qs.reserve(extra + qt_layout(c, append_max_chunk(), nfin, nfin).doubles))
+        return e;
     HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, nfin, nfin, P, s));
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
     {
@@ -146,7 +142,6 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
         c->hInfo[0] = 0; // (the re-run repeats the solve, the tail and the sweeps from the untouched inputs)
         (void)append_enqueue(c, Xb, nb0, rem, extra, slices_cap);
     });
-    query_release(c);
     if (rc < 0)
         return rc;
     return status != 0 ? status : rc;

@@ -223,17 +223,18 @@ int ld_pad() { return 16; } // break power-of-two column strides (HBM channel ca
 // power-of-two column strides
 int64_t ld_for(int64_t cap, int P) { return cap + round_up((int64_t)P + ld_pad(), 16); }
 
-hipEvent_t get_event(gpe_ctx* c)
+hipEvent_t get_event(std::vector<hipEvent_t>& pool)
 {
-    if (!c->pool.empty()) {
-        hipEvent_t e = c->pool.back();
-        c->pool.pop_back();
+    if (!pool.empty()) {
+        hipEvent_t e = pool.back();
+        pool.pop_back();
         return e;
     }
     hipEvent_t e;
     hipEventCreate(&e);
     return e;
 }
+hipEvent_t get_event(gpe_ctx* c) { return get_event(c->pool); }
 
 // roctx ranges around every phase (tracing), so that a rocprofv3 --marker-trace timeline carries the phase
 // names.  Off unless GPE_ROCTX=1; libroctx64 is looked up at run time (no link-time dependency of the product on it).

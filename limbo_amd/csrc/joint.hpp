@@ -6,8 +6,7 @@
 // the partial matrices of the split are M x M each
 static int64_t joint_max_points(const gpe_ctx* c)
 {
-    const int64_t by_chunk = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(c->N, 1)) / 64 * 64);
-    return std::min<int64_t>(by_chunk, 16384);
+    return qt_rows_per_chunk(c->N, 16384);
 }
 
 // The private scratch context that owns Sigma and factors it.  potrf_blocked takes the matrix as an argument but the leading
@@ -91,10 +90,10 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     hipStream_t s = c->stream;
     digest_kernel(c);
     const int64_t N = c->N;
-    const int D = c->D, P = c->P;
+    const int P = c->P;
     // Fewer samples than one outer panel (or a panel width the transposed layout does not serve): the N x M layout of
     // query_impl — Z = L^-1 Ks by the blocked solve, k-contiguous operands — and the composed covariance path only
-    const bool transposed = c->nbo % 128 == 0 && c->nbo <= 256 && N >= c->nbo;
+    const bool transposed = qt_serves(c); // (GPE_QUERY_T is not asked here)
     const bool want_cov = cov != nullptr || dr != nullptr;
     gpe_ctx* sc = nullptr;
     if (want_cov) {
@@ -109,26 +108,16 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     const bool splitk = transposed && joint_use_splitk(M, cus);
     const int nch = want_cov && splitk ? joint_cov_chunks(M, N, cus) : 0;
     const int64_t mc_max = round_up(M, 64);
-    QtBufs b = qt_layout(c, mc_max, N16);
-    if (!transposed) { // Kst holds Ks (ld x mc_max, k-contiguous columns), solved in place; no Zt, panels or partial sums
-        b.ldq = mc_max;
-        b.n_qt = (size_t)(b.ldq * std::max(xt_rows(D), 1));
-        b.n_kst = (size_t)(c->ld * mc_max);
-        b.n_zt = b.n_xp = b.n_part = 0;
-        b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_kta + 2 * (size_t)mc_max;
-    }
+    QtBufs b = transposed ? qt_layout(c, mc_max, N16) : nm_layout(c, mc_max, false);
     const int ncols = dr ? dr->S * P : 0;
     const int64_t nt = (M + 127) / 128, nitems = nt * (nt + 1) / 2 * std::max(nch, 0);
     const size_t n_part = (size_t)nch * (size_t)(b.ldq * M);              // the partial matrices, ldq x M each
     const size_t n_items = (sizeof(GemmItem) * (size_t)nitems + 7) / 8;   // (in doubles)
     const size_t n_bins = (sizeof(int32_t) * (size_t)(nitems + 1) + 7) / 8;
     const size_t n_z = (size_t)M * ncols, n_mq = dr && dr->mean_q ? (size_t)M * P : 0, n_am = 2 * (size_t)ncols;
-    {
-        const int e = query_reserve(c, sizeof(double) * (b.doubles + n_part + n_items + n_bins + 2 * n_z + n_mq + n_am));
-        if (e)
-            return e;
-    }
-    qt_carve(b, c->dQuery);
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b, n_part + n_items + n_bins + 2 * n_z + n_mq + n_am))
+        return e;
     double* dPartM = b.dKvv + b.mc_max;
     GemmItem* dItems = (GemmItem*)(dPartM + n_part);
     int32_t* dBins = (int32_t*)((double*)dItems + n_items);
@@ -138,32 +127,12 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     double* dAm = dMq + n_mq;
 
     // (profiling: the call's own phases — Z, Sigma, the factorisation, the draws — for gpe_joint_phase_ms)
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto mark = [&](int i) {
-        if (c->prof) {
-            ev[i] = get_event(c);
-            hipEventRecord(ev[i], s);
-        }
-    };
-    mark(0);
+    Marks mk(c->pool, s, c->prof);
+    const int t0 = mk.mark();
     if (!transposed) {
-        const int64_t ld = c->ld;
-        hipMemcpyAsync(b.dQrm, Xq, sizeof(double) * (size_t)(M * D), hipMemcpyHostToDevice, s);
-        launch_transpose_x(s, b.dQrm, M, D, b.dQt, b.ldq, 0);
-        project_lambda(c, s, b.dQt, b.ldq, 0, M);
-        {
-            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-            launch_build_Ks(s, c->dXt, ld, N, b.dQt, b.ldq, M, c->kp, b.dKst, ld); // gp.hpp:626-632
-        }
-        if (kta || dr) {
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * M * P);
-            launch_kta(s, b.dKst, ld, N, M, c->dAl, ld, P, b.dKta, mc_max); // gp.hpp:615
-            if (kta)
-                for (int p = 0; p < P; ++p)
-                    hipMemcpyAsync(kta + (int64_t)p * M, b.dKta + (int64_t)p * mc_max, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, s);
-        }
+        chunk_head(c, b, Xq, true, M, true, kta != nullptr || dr != nullptr, kta, 0, M);
         if (want_cov)
-            trsm_left_blocked(c, c->dA, b.dKst, ld, N, M, false, GPE_PH_QUERY); // gp.hpp:620
+            trsm_left_blocked(c, c->dA, b.dKst, c->ld, N, M, false, GPE_PH_QUERY); // gp.hpp:620
     }
     else {
         if (want_cov) {
@@ -173,7 +142,7 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         }
         qt_chunk(c, b, Xq, M, kta != nullptr || dr != nullptr, kta, 0, M, want_cov);
     }
-    mark(1);
+    const int t1 = mk.mark();
     std::vector<GemmItem> items; // (host copies of the launch list: alive until the stream has been waited for, below)
     std::vector<int32_t> bins;
     if (want_cov && splitk) {
@@ -223,7 +192,8 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         launch_gemm_sub(s, g);
         launch_symmetrize_from_lower(s, sc->dKhost, sc->ld, M);
     }
-    mark(2);
+    const int t2 = mk.mark();
+    int t3 = -1, t4 = -1;
     if (cov)
         HIPCHK(c, copy2d_to_host(cov, ldc, sc->dKhost, sc->ld, M, M, s));
     if (dr && ncols > 0) {
@@ -251,14 +221,14 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
             c->joint_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
         if (rc == GPE_OK && ncols > 0) {
-            mark(3);
+            t3 = mk.mark();
             {
                 PhaseScope ps(c, GPE_PH_QUERY, (double)M * M * ncols);
                 launch_draws(s, sc->dA, sc->ld, M, dZn, n_mq ? dMq : nullptr, b.dKta, b.mc_max, dr->S, ncols, dF);
                 if (dr->argmax || dr->fmax)
                     launch_argmax(s, dF, M, ncols, dAm);
             }
-            mark(4);
+            t4 = mk.mark();
             std::vector<double> am(n_am);
             if (dr->F)
                 HIPCHK(c, hipMemcpyAsync(dr->F, dF, sizeof(double) * n_z, hipMemcpyDeviceToHost, s));
@@ -278,22 +248,13 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         }
     }
     if (c->prof) { // (every stream wait above has passed: the events are complete)
-        const int pair[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-        const int slot[3] = {0, 1, 3};
-        for (int q = 0; q < 3; ++q) {
-            float ms = 0.f;
-            if (ev[pair[q][0]] && ev[pair[q][1]] && hipEventSynchronize(ev[pair[q][1]]) == hipSuccess)
-                hipEventElapsedTime(&ms, ev[pair[q][0]], ev[pair[q][1]]);
-            c->joint_ms[slot[q]] = ms;
-        }
+        c->joint_ms[0] = mk.ms(t0, t1);
+        c->joint_ms[1] = mk.ms(t1, t2);
+        c->joint_ms[3] = mk.ms(t3, t4);
         if (!dr)
             c->joint_ms[2] = 0.0;
-        for (hipEvent_t e : ev)
-            if (e)
-                c->pool.push_back(e);
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }
 

@@ -20,7 +20,7 @@ struct gpe_paths_ctx {
     DevBuf<double> dU;     // ldx x ncols
     DevBuf<double> dWork;  // an evaluation's chunk buffers, kept between calls
     int nsegF = 1, nsegK = 1;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<hipEvent_t> pool; // the events of its phase timers (Marks): its own — an evaluation does not hold the handle's mutex
     double ms[4] = {0, 0, 0, 0};
 };
 
@@ -55,7 +55,7 @@ static bool all_finite(const double* a, size_t n)
 // U for the draws [c0, c0 + nc): features at X, the residual (transposed, nc x N with leading dimension ldt, at dRt), then `solve`
 // turns it into Wt = Rt K^-1 at the address it returns, and Wt^T goes into the set.  On the handle's stream, its mutex held.
 static int paths_columns(gpe_ctx* c, gpe_paths_ctx* ps, const double* E, int c0, int nc, double* dRt, int64_t ldt, DevBuf<double>& tmp,
-                         hipEvent_t* ev, const std::function<const double*()>& solve)
+                         const std::function<const double*()>& solve)
 {
     hipStream_t s = c->stream;
     const int64_t N = c->N;
@@ -66,7 +66,8 @@ static int paths_columns(gpe_ctx* c, gpe_paths_ctx* ps, const double* E, int c0,
     double* dE = dPart + n_part;
     if (E)
         HIPCHK(c, hipMemcpyAsync(dE, E + (size_t)N * c0, sizeof(double) * n_e, hipMemcpyHostToDevice, s));
-    hipEventRecord(ev[0], s);
+    Marks mk(ps->pool, s, true); // (the set is not shared yet)
+    mk.mark();
     for (int64_t i0 = 0; i0 < N; i0 += pc_max) {
         const int64_t pc = std::min<int64_t>(pc_max, N - i0);
         PhaseScope sc(c, GPE_PH_QUERY, 2.0 * pc * ps->R * nc);
@@ -75,19 +76,16 @@ static int paths_columns(gpe_ctx* c, gpe_paths_ctx* ps, const double* E, int c0,
         launch_paths_residual(s, dPart, ps->nsegF, pc_max, nc, pc, i0, c->dOm, c->ld, ps->S, c0, E ? dE : nullptr, N,
                               std::sqrt(c->noise + 1e-8), dRt, ldt);
     }
-    hipEventRecord(ev[1], s);
+    mk.mark();
     const double* dWt = solve();
     launch_paths_untranspose(s, dWt, ldt, N, nc, ps->dU + (int64_t)c0 * ps->ldx, ps->ldx);
-    hipEventRecord(ev[2], s);
+    mk.mark();
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
         c->err = "paths_create: stream sync failed";
         return GPE_ERR_HIP;
     }
-    for (int q = 0; q < 2; ++q) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess)
-            ps->ms[q] += ms;
-    }
+    for (int q = 0; q < 2; ++q)
+        ps->ms[q] += mk.ms(q, q + 1);
     return GPE_OK;
 }
 
@@ -95,74 +93,48 @@ static int paths_columns(gpe_ctx* c, gpe_paths_ctx* ps, const double* E, int c0,
 static int paths_solve_transposed(gpe_ctx* c, gpe_paths_ctx* ps, const double* E)
 {
     const int64_t N = c->N;
-    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64); // (the query's rule)
-    mc_max = std::min<int64_t>(mc_max, round_up(ps->ncols, 64));
+    const int64_t mc_max = qt_rows_per_chunk(N, ps->ncols);
     QtBufs b = qt_layout(c, mc_max, N);
-    {
-        const int e = query_reserve(c, sizeof(double) * b.doubles);
-        if (e)
-            return e;
-    }
-    qt_carve(b, c->dQuery);
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b))
+        return e;
     qt_panels(c, b);
     DevBuf<double> tmp;
     int rc = GPE_OK;
     for (int c0 = 0; c0 < ps->ncols && rc == GPE_OK; c0 += (int)mc_max) {
         const int nc = (int)std::min<int64_t>(mc_max, ps->ncols - c0);
-        rc = paths_columns(c, ps, E, c0, nc, b.dKst, b.ldq, tmp, ps->ev, [&]() -> const double* {
+        rc = paths_columns(c, ps, E, c0, nc, b.dKst, b.ldq, tmp, [&]() -> const double* {
             qt_forward(c, b, nc);
             qt_backward(c, b, nc);
             return b.dKst;
         });
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }
 
 // Where the transposed layout does not serve the model: Wt = Rt K^-1 in one product (K^-1: ensure_inv, as qgrad_by_inverse)
 static int paths_solve_by_inverse(gpe_ctx* c, gpe_paths_ctx* ps, const double* E)
 {
-    hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld;
     {
         const int e = ensure_inv(c);
         if (e)
             return e;
     }
-    int64_t mc_max = std::max<int64_t>(64, ((int64_t)1 << 28) / std::max<int64_t>(ld, 1)); // (query_impl's rule)
-    mc_max = round_up(std::min<int64_t>(mc_max, round_up(ps->ncols, 64)), 64);
-    const int64_t ldt = mc_max + 16;
-    const int qtile = qt_layout(c, mc_max, N).qtile;
+    const int64_t mc_max = nm_cols_per_chunk(ld, ps->ncols), ldt = mc_max + 16;
     DevBuf<double> mats, tmp;
     const size_t n_t = (size_t)(ldt * N), n_ki = (size_t)(ld * N);
     HIPCHK(c, mats.reserve(2 * n_t + n_ki));
     double* dRt = mats;
     double* dWt = dRt + n_t;
     double* dKi = dWt + n_t;
-    {
-        PhaseScope sc(c, GPE_PH_QUERY, 0.0);
-        launch_copy2d(s, c->dKinv, ld, dKi, ld, N, N);
-        launch_symmetrize_from_lower(s, dKi, ld, N);
-    }
+    kinv_operand(c, dKi);
     int rc = GPE_OK;
     for (int c0 = 0; c0 < ps->ncols && rc == GPE_OK; c0 += (int)mc_max) {
         const int nc = (int)std::min<int64_t>(mc_max, ps->ncols - c0);
-        rc = paths_columns(c, ps, E, c0, nc, dRt, ldt, tmp, ps->ev, [&]() -> const double* {
-            GemmArgs g{};
-            g.C = dWt;
-            g.ldc = ldt;
-            g.A = dRt;
-            g.lda = ldt;
-            g.B = dKi;
-            g.ldb = ld;
-            g.m = nc;
-            g.n = N;
-            g.k = N;
-            g.overwrite = 1;
-            g.tile = qtile;
-            PhaseScope sc(c, GPE_PH_QUERY, gemm_flops(g));
-            launch_gemm_sub(s, g);
+        rc = paths_columns(c, ps, E, c0, nc, dRt, ldt, tmp, [&]() -> const double* {
+            times_kinv(c, dKi, dRt, dWt, ldt, nc);
             return dWt;
         });
     }
@@ -175,9 +147,8 @@ static void paths_free(gpe_paths_ctx* ps)
     hipSetDevice(ps->device);
     if (ps->stream)
         hipStreamSynchronize(ps->stream);
-    for (hipEvent_t& e : ps->ev)
-        if (e)
-            hipEventDestroy(e);
+    for (hipEvent_t e : ps->pool)
+        hipEventDestroy(e);
     if (ps->stream)
         hipStreamDestroy(ps->stream);
     delete ps; // (the DevBufs free themselves)
@@ -221,8 +192,6 @@ int gpe_paths_create(gpe_handle c, int R, int S, const double* Omega0, const dou
     ps->nsegF = paths_nseg(R, ncols);
     ps->nsegK = paths_nseg(N, ncols);
     HIPCHK(c, hipStreamCreateWithFlags(&ps->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : ps->ev)
-        HIPCHK(c, hipEventCreate(&e));
     HIPCHK(c, ps->dXt.reserve((size_t)(ps->ldx * Rr)));
     HIPCHK(c, ps->dOm.reserve((size_t)(ps->ldr * Rr)));
     HIPCHK(c, ps->dPhase.reserve((size_t)ps->ldr));
@@ -245,9 +214,7 @@ int gpe_paths_create(gpe_handle c, int R, int S, const double* Omega0, const dou
     HIPCHK(c, hipMemcpyAsync(ps->dPhase, phase, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, s));
     launch_paths_scale_rows(s, c->dXt, c->ld, ps->dXt, ps->ldx, N, ps->kp);
 
-    static const bool transposed_ok = env_not_zero("GPE_QUERY_T"); // (as gpe_query_batch_grad)
-    const int rc = transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && N >= c->nbo ? paths_solve_transposed(c, ps, E)
-                                                                                      : paths_solve_by_inverse(c, ps, E);
+    const int rc = qt_enabled(c) ? paths_solve_transposed(c, ps, E) : paths_solve_by_inverse(c, ps, E);
     if (hipStreamSynchronize(s) != hipSuccess) // (the staging vectors, on every path)
         return GPE_ERR_HIP;
     if (rc)
@@ -296,13 +263,14 @@ static int paths_eval_impl(gpe_paths_ctx* ps, const double* Xq, int64_t T, const
         launch_transpose_x(s, dQrm, mc, D, dQt, ldq, 0);
         if (ps->kp.k_lam > 0)
             launch_lambda_rows(s, dQt, ldq, 0, mc, ps->lp);
-        hipEventRecord(ps->ev[0], s);
+        Marks mk(ps->pool, s, true);
+        mk.mark();
         launch_paths_basis(s, 0, grad, dQt, ldq, mc, ps->dOm, ps->ldr, ps->R, ps->dPhase, ps->dW, ps->ldr, ncols, ps->kp, ps->nsegF, dPf, mc_max);
-        hipEventRecord(ps->ev[1], s);
+        mk.mark();
         launch_paths_basis(s, 1, grad, dQt, ldq, mc, ps->dXt, ps->ldx, N, nullptr, ps->dU, ps->ldx, ncols, ps->kp, ps->nsegK, dPk, mc_max);
         launch_paths_fold(s, dPf, ps->nsegF, dPk, ps->nsegK, mc_max, NS, ncols, mc, ps->kp, ps->lp, mean_q ? dMq : nullptr, mc_max, ps->S,
                           (F || want_am) ? dFo : nullptr, mc_max, grad ? dGo : nullptr, mc_max);
-        hipEventRecord(ps->ev[2], s);
+        mk.mark();
         if (want_am)
             launch_paths_argmax(s, dFo, mc_max, mc, ncols, t0, t0 == 0, dAm);
         if (F)
@@ -312,11 +280,8 @@ static int paths_eval_impl(gpe_paths_ctx* ps, const double* Xq, int64_t T, const
         if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess)
             rc = GPE_ERR_HIP;
         else
-            for (int q = 0; q < 2; ++q) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ps->ev[q], ps->ev[q + 1]) == hipSuccess)
-                    ps->ms[2 + q] += ms;
-            }
+            for (int q = 0; q < 2; ++q)
+                ps->ms[2 + q] += mk.ms(q, q + 1);
     }
     if (rc == GPE_OK && want_am) {
         std::vector<double> am(n_am);
@@ -329,7 +294,7 @@ static int paths_eval_impl(gpe_paths_ctx* ps, const double* Xq, int64_t T, const
                 memcpy(argmax + q, &am[2 * (size_t)q + 1], sizeof(int64_t));
         }
     }
-    if (sizeof(double) * ps->dWork.capacity() > ((size_t)64 << 20)) // a large batch: give the memory back (as query_release)
+    if (sizeof(double) * ps->dWork.capacity() > ((size_t)64 << 20)) // a large batch: give the memory back (as QueryScratch)
         ps->dWork.reset();
     return rc;
 }

@@ -2,34 +2,13 @@
 // A part of engine.hip's translation unit (included there, once, behind query.hpp, whose chunk helpers it shares).
 #pragma once
 
-// the call's own phases — forward part, backward solve, gradient kernel — for gpe_query_grad_phase_ms: four events per chunk,
-// read after the chunk's stream wait
-struct QgMarks {
-    gpe_ctx* c;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    explicit QgMarks(gpe_ctx* c_) : c(c_) {}
-    void mark(int i)
-    {
-        if (c->prof) {
-            ev[i] = get_event(c);
-            hipEventRecord(ev[i], c->stream);
-        }
-    }
-    void collect() // (the stream has been waited for)
-    {
-        for (int q = 0; q < 3; ++q) {
-            float ms = 0.f;
-            if (ev[q] && ev[q + 1] && hipEventSynchronize(ev[q + 1]) == hipSuccess)
-                hipEventElapsedTime(&ms, ev[q], ev[q + 1]);
-            c->qgrad_ms[q] += ms;
-        }
-        for (hipEvent_t& e : ev) {
-            if (e)
-                c->pool.push_back(e);
-            e = nullptr;
-        }
-    }
-};
+// the call's own phases — forward part, backward solve, gradient kernel — for gpe_query_grad_phase_ms: four boundaries per chunk
+// (a Marks of its own), added up over the chunks after each chunk's stream wait
+static void qg_collect(gpe_ctx* c, const Marks& mk)
+{
+    for (int q = 0; q < 3; ++q)
+        c->qgrad_ms[q] += mk.ms(q, q + 1);
+}
 
 // the gradient columns of one chunk: the pass over Wt / alpha, and the results to the caller's arrays
 //   Qt: the chunk's SoA points (ldq), Wt: mc x N (ldw) or null; dPartG / dG: scratch (qg_extra)
@@ -111,19 +90,15 @@ static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
     hipStream_t s = c->stream;
     const int64_t N = c->N;
     const int D = c->D;
-    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64); // (the query's rule)
-    mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
+    const int64_t mc_max = qt_rows_per_chunk(N, M);
     QtBufs b = qt_layout(c, mc_max, N);
     size_t n_partg = 0, n_g = 0;
     const bool grads = dkta || dvar, want_z = var || dvar;
     if (grads)
         qg_extra(c, b.nseg, b.ldq, mc_max, &n_partg, &n_g);
-    {
-        const int e = query_reserve(c, sizeof(double) * (b.doubles + n_partg + n_g));
-        if (e)
-            return e;
-    }
-    qt_carve(b, c->dQuery);
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b, n_partg + n_g))
+        return e;
     double* dPartG = b.dKvv + b.mc_max;
     double* dG = dPartG + n_partg;
     int rc = GPE_OK;
@@ -131,8 +106,8 @@ static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
         qt_panels(c, b);
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0), ldq = b.ldq;
-        QgMarks mk(c);
-        mk.mark(0);
+        Marks mk(c->pool, s, c->prof);
+        mk.mark();
         qt_chunk(c, b, Xq + m0 * D, mc, kta != nullptr, kta, m0, M, want_z);
         if (var) { // (before Zt is consumed below)
             PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
@@ -140,21 +115,20 @@ static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
             launch_row_var_t(s, b.dZt, ldq, N, mc, b.dKvv, b.dVar, b.dPart, ldq, b.nseg); // gp.hpp:621
             hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
-        mk.mark(1);
+        mk.mark();
         if (dvar)
             qt_backward(c, b, mc);
-        mk.mark(2);
+        mk.mark();
         if (grads)
             qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? b.dKst : nullptr, ldq, b.nseg, dPartG, dG, dkta, dvar, m0, M);
-        mk.mark(3);
+        mk.mark();
         if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
             c->err = "query_batch_grad: stream sync failed";
             rc = GPE_ERR_HIP;
         }
-        mk.collect();
+        qg_collect(c, mk);
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }
 
@@ -164,102 +138,62 @@ static int qgrad_by_inverse(gpe_ctx* c, const double* Xq, int64_t M, double* kta
 {
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld;
-    const int D = c->D, P = c->P;
+    const int D = c->D;
     if (dvar) {
         const int e = ensure_inv(c);
         if (e)
             return e;
     }
-    int64_t mc_max = std::max<int64_t>(64, ((int64_t)1 << 28) / std::max<int64_t>(ld, 1)); // (query_impl's rule)
-    mc_max = round_up(std::min<int64_t>(mc_max, round_up(M, 64)), 64);
-    const int64_t ldq = mc_max, ldt = mc_max + 16;
-    const int nseg = qt_layout(c, mc_max, N).nseg, qtile = qt_layout(c, mc_max, N).qtile;
+    const int64_t mc_max = nm_cols_per_chunk(ld, M), ldt = mc_max + 16;
+    QtBufs b = nm_layout(c, mc_max, false);
+    const int64_t ldq = b.ldq;
     const bool grads = dkta || dvar;
-    const size_t n_qrm = (size_t)(mc_max * std::max(D, 1)), n_qt = (size_t)(ldq * std::max(xt_rows(D), 1));
-    const size_t n_ks = (size_t)(ld * mc_max), n_kta = (size_t)(mc_max * P);
     const size_t n_t = dvar ? (size_t)(ldt * N) : 0, n_ki = dvar ? (size_t)(ld * N) : 0;
     size_t n_partg = 0, n_g = 0;
     if (grads)
-        qg_extra(c, nseg, ldt, mc_max, &n_partg, &n_g);
-    {
-        const int e = query_reserve(c, sizeof(double) * (n_qrm + n_qt + n_ks + n_kta + 2 * (size_t)mc_max + 2 * n_t + n_ki + n_partg + n_g));
-        if (e)
-            return e;
-    }
-    double* dQrm = c->dQuery;
-    double* dQt = dQrm + n_qrm;
-    double* dKs = dQt + n_qt;
-    double* dKta = dKs + n_ks;
-    double* dVar = dKta + n_kta;
-    double* dKvv = dVar + mc_max;
-    double* dKst = dKvv + mc_max; // the cross kernel with the points contiguous
+        qg_extra(c, b.nseg, ldt, mc_max, &n_partg, &n_g);
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b, 2 * n_t + n_ki + n_partg + n_g))
+        return e;
+    double* dKst = b.dKvv + mc_max; // the cross kernel with the points contiguous
     double* dWt = dKst + n_t;
     double* dKi = dWt + n_t;
     double* dPartG = dKi + n_ki;
     double* dG = dPartG + n_partg;
-    if (dvar) {
-        PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-        launch_copy2d(s, c->dKinv, ld, dKi, ld, N, N);
-        launch_symmetrize_from_lower(s, dKi, ld, N);
-    }
+    if (dvar)
+        kinv_operand(c, dKi);
     int rc = GPE_OK;
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        QgMarks mk(c);
-        mk.mark(0);
-        hipMemcpyAsync(dQrm, Xq + m0 * D, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
-        launch_transpose_x(s, dQrm, mc, D, dQt, ldq, 0);
-        project_lambda(c, s, dQt, ldq, 0, mc);
-        if (kta || var) {
-            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-            launch_build_Ks(s, c->dXt, ld, N, dQt, ldq, mc, c->kp, dKs, ld); // gp.hpp:626-632
-        }
-        if (kta) {
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
-            launch_kta(s, dKs, ld, N, mc, c->dAl, ld, P, dKta, mc_max); // gp.hpp:615
-            for (int p = 0; p < P; ++p)
-                hipMemcpyAsync(kta + m0 + (int64_t)p * M, dKta + (int64_t)p * mc_max, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
-        }
+        Marks mk(c->pool, s, c->prof);
+        mk.mark();
+        chunk_head(c, b, Xq + m0 * D, true, mc, kta || var, kta != nullptr, kta, m0, M);
         if (var) {
-            trsm_left_blocked(c, c->dA, dKs, ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
+            trsm_left_blocked(c, c->dA, b.dKst, ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
             PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, dQt, ldq, mc, c->kp, dKvv);
-            launch_col_var(s, dKs, ld, N, mc, dKvv, dVar); // gp.hpp:621
-            hipMemcpyAsync(var + m0, dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+            launch_kvv(s, b.dQt, ldq, mc, c->kp, b.dKvv);
+            launch_col_var(s, b.dKst, ld, N, mc, b.dKvv, b.dVar); // gp.hpp:621
+            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
-        mk.mark(1);
+        mk.mark();
         if (dvar) {
             {
                 PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-                launch_build_Ks(s, dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldt); // k is symmetric: the transposed block
+                launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldt); // k is symmetric: the transposed block
             }
-            GemmArgs g{};
-            g.C = dWt;
-            g.ldc = ldt;
-            g.A = dKst;
-            g.lda = ldt;
-            g.B = dKi;
-            g.ldb = ld;
-            g.m = mc;
-            g.n = N;
-            g.k = N;
-            g.overwrite = 1;
-            g.tile = qtile;
-            PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
-            launch_gemm_sub(s, g);
+            times_kinv(c, dKi, dKst, dWt, ldt, mc);
         }
-        mk.mark(2);
+        mk.mark();
         if (grads)
-            qg_columns(c, dQt, ldq, mc, mc_max, dvar ? dWt : nullptr, ldt, nseg, dPartG, dG, dkta, dvar, m0, M);
-        mk.mark(3);
+            qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? dWt : nullptr, ldt, b.nseg, dPartG, dG, dkta, dvar, m0, M);
+        mk.mark();
         if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
             c->err = "query_batch_grad: stream sync failed";
             rc = GPE_ERR_HIP;
         }
-        mk.collect();
+        qg_collect(c, mk);
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }
 
@@ -278,8 +212,7 @@ int gpe_query_batch_grad(gpe_handle c, const double* Xq, int64_t M, double* kta,
     digest_kernel(c);
     for (double& ms : c->qgrad_ms)
         ms = 0.0;
-    static const bool transposed_ok = env_not_zero("GPE_QUERY_T"); // (as query_impl)
-    if (transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo)
+    if (qt_enabled(c))
         return qgrad_transposed(c, Xq, M, kta, var, dkta, dvar);
     return qgrad_by_inverse(c, Xq, M, kta, var, dkta, dvar);
 }

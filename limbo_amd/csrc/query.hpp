@@ -12,9 +12,39 @@
 // of the direct-to-LDS matrix-core kernel (gemm.hip, k_gemm_glds), as K^-1's U = L^-T (ensure_inv).  The N x M layout
 // (rounds 1-2, still the path for caller-supplied cross kernels) has the right-hand sides k-contiguous and ran its
 // M N^2 flops through the register-staged kernel: 38 TFLOP/s at N = 16384 against the 53 of the factorisation's updates.
-// The buffers of one chunk of <= mc_max points, carved from gpe_ctx::dQuery, and the launches that fill them — shared by
-// query_transposed (the marginals) and the joint posterior (joint.hpp), which keeps Zt for all its points at once.
+// The helpers below are what every query-side call is built from (qgrad.hpp, pathwise.hpp, joint.hpp, append.hpp, sparse.hpp,
+// sparse_grad.hpp, included behind this file): the layout decision, the chunk size, the buffers, a chunk's head, the panel solve,
+// K^-1 as an operand, the scratch's lease and the phase timer.
+
+// Which layout.  The transposed one serves a context whose outer panels are what the one-launch panel inverses take (inv.hip) and
+// that has at least one of them; the marginal calls (query, gradients, path sets) also obey GPE_QUERY_T, read once per process.
+// The joint posterior and the sparse model ask qt_serves alone; the blocked append goes point by point while it is false.
+static bool qt_serves(const gpe_ctx* c) { return c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo; }
+static bool qt_enabled(const gpe_ctx* c)
+{
+    static const bool allowed = env_not_zero("GPE_QUERY_T");
+    return allowed && qt_serves(c);
+}
+// Points per chunk: a chunk's matrices (points x N transposed, ld x points otherwise) stay under 2 GiB each, and no chunk is larger
+// than the batch rounded up to 64.  From the model's size and M alone.
+static const int64_t kChunkDoubles = (int64_t)1 << 28;
+static int64_t qt_rows_per_chunk(int64_t N, int64_t M)
+{
+    return std::min<int64_t>(std::max<int64_t>(64, (kChunkDoubles / std::max<int64_t>(N, 1)) / 64 * 64), round_up(M, 64));
+}
+static int64_t nm_cols_per_chunk(int64_t ld, int64_t M)
+{
+    return round_up(std::min<int64_t>(std::max<int64_t>(64, kChunkDoubles / std::max<int64_t>(ld, 1)), round_up(M, 64)), 64);
+}
+// The tile of every product of a chunk is picked from N alone, never from the batch: the 128 x 128 and the 64 x 64 kernels round
+// differently in the last bit (measured, round 6: a point's variance moved by 1.5e-15 with the size of the batch it was asked
+// in, because launch_gemm_sub picks the tile from the live-tile count = from mc).  A point's answer must not depend on the
+// batch around it (tests/test_gpu_configs.py: the 100 000-point batch of configs[2] bitwise equal to chunks of 4096).
+static int qt_tile(int64_t N) { return N >= 1024 ? 128 : 64; }
+
+// The buffers of one chunk of <= mc_max points, carved from gpe_ctx::dQuery, and the launches that fill them
 struct QtBufs {
+    bool transposed = true; // false: the N x M layout (nm_layout)
     int64_t mc_max = 0, ldq = 0, npan = 0, zcols = 0;
     int nseg = 1, qtile = 128;
     size_t n_qrm = 0, n_qt = 0, n_kst = 0, n_zt = 0, n_xp = 0, n_part = 0, n_kta = 0, doubles = 0;
@@ -41,11 +71,7 @@ static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols, int64_t
     b.n_part = (size_t)b.nseg * std::max(P, 1) * (size_t)b.ldq;
     b.n_kta = (size_t)(mc_max * P);
     b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_xp + b.n_part + b.n_kta + 2 * (size_t)mc_max;
-    // The tile of every product below is picked from N alone, never from the batch: the 128 x 128 and the 64 x 64 kernels round
-    // differently in the last bit (measured, round 6: a point's variance moved by 1.5e-15 with the size of the batch it was asked
-    // in, because launch_gemm_sub picks the tile from the live-tile count = from mc).  A point's answer must not depend on the
-    // batch around it (tests/test_gpu_configs.py: the 100 000-point batch of configs[2] bitwise equal to chunks of 4096).
-    b.qtile = N >= 1024 ? 128 : 64;
+    b.qtile = qt_tile(N);
     return b;
 }
 static void qt_carve(QtBufs& b, double* base)
@@ -60,39 +86,106 @@ static void qt_carve(QtBufs& b, double* base)
     b.dVar = b.dKta + b.n_kta;
     b.dKvv = b.dVar + b.mc_max;
 }
-// grow gpe_ctx::dQuery to `bytes` (contents are not kept)
-static int query_reserve(gpe_ctx* c, size_t bytes)
+// The N x M layout in the same buffers — fewer samples than one outer panel, a panel width the transposed layout does not serve,
+// GPE_QUERY_T=0, caller-supplied cross kernels: Kst holds Ks (ld x mc_max, the samples contiguous) and is solved in place
+// (trsm_left_blocked); no panel inverses, no partial sums; second: Zt is another matrix of that shape, else empty
+static QtBufs nm_layout(const gpe_ctx* c, int64_t mc_max, bool second)
 {
-    HIPCHK(c, c->dQuery.reserve((bytes + sizeof(double) - 1) / sizeof(double)));
-    return GPE_OK;
+    QtBufs b = qt_layout(c, mc_max, c->N);
+    b.transposed = false;
+    b.ldq = mc_max;
+    b.n_qt = (size_t)(b.ldq * std::max(xt_rows(c->D), 1));
+    b.n_kst = (size_t)(c->ld * mc_max);
+    b.n_zt = second ? b.n_kst : 0;
+    b.n_xp = b.n_part = 0;
+    b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_kta + 2 * (size_t)mc_max;
+    return b;
 }
-static void query_release(gpe_ctx* c)
-{
-    if (sizeof(double) * c->dQuery.capacity() > ((size_t)64 << 20)) // a large batch: give the memory back
-        c->dQuery.reset();
-}
+extern "C++" {
+namespace { // (file-local types with member functions: nothing of them is exported)
+// gpe_ctx::dQuery for the length of one call: grown on request (contents are not kept) and, however the call ends, given back
+// when a large batch has made it large — kept across calls while small, so that point queries do not malloc/free
+struct QueryScratch {
+    gpe_ctx* c;
+    explicit QueryScratch(gpe_ctx* c_) : c(c_) {}
+    QueryScratch(const QueryScratch&) = delete;
+    ~QueryScratch() { release(); }
+    void release() // (a call with more work behind its last chunk says so itself, early)
+    {
+        if (sizeof(double) * c->dQuery.capacity() > ((size_t)64 << 20))
+            c->dQuery.reset();
+    }
+    int reserve(size_t doubles)
+    {
+        HIPCHK(c, c->dQuery.reserve(doubles));
+        return GPE_OK;
+    }
+    // room for b and `extra` doubles behind it (from b.dKvv + b.mc_max on); b carved
+    int carve(QtBufs& b, size_t extra = 0)
+    {
+        const int e = reserve(b.doubles + extra);
+        if (e == GPE_OK)
+            qt_carve(b, c->dQuery);
+        return e;
+    }
+};
+
+// The call's own phases for the *_phase_ms exports: boundaries recorded on one stream with events of one pool (the handle's, under
+// its mutex; a path set's own), and — after the caller's stream wait — the time between two of them.  Off: mark() records nothing
+// and every interval is 0.  The events go back to the pool with the timer, on every way out of the call.
+struct Marks {
+    std::vector<hipEvent_t>& pool;
+    hipStream_t s;
+    bool on;
+    std::vector<hipEvent_t> ev;
+    Marks(std::vector<hipEvent_t>& pool_, hipStream_t s_, bool on_) : pool(pool_), s(s_), on(on_) {}
+    Marks(const Marks&) = delete;
+    ~Marks()
+    {
+        for (hipEvent_t e : ev)
+            pool.push_back(e);
+    }
+    int mark() // the index of the boundary, -1 while off
+    {
+        if (!on)
+            return -1;
+        ev.push_back(get_event(pool));
+        hipEventRecord(ev.back(), s);
+        return (int)ev.size() - 1;
+    }
+    int count() const { return (int)ev.size(); }
+    double ms(int i, int j) const
+    {
+        float t = 0.f;
+        if (i >= 0 && j >= 0 && j < count() && hipEventSynchronize(ev[(size_t)j]) == hipSuccess)
+            hipEventElapsedTime(&t, ev[(size_t)i], ev[(size_t)j]);
+        return t;
+    }
+};
+} // namespace
+} // extern "C++"
+
 // X_p of every panel, compact (in front of the first chunk whose Zt is wanted)
 static void qt_panels(gpe_ctx* c, const QtBufs& b)
 {
     PhaseScope ps(c, GPE_PH_QUERY, 0.0);
     launch_inv_panels(c->stream, c->dA, c->ld, c->N, (int)c->nbo, c->dXinv, b.dXp, 0, nullptr, 0);
 }
-// Zt = Kst L^-T for the mc rows of b.dKst — a chunk's cross kernel, or right-hand sides a caller put in its place (pathwise.hpp);
-// Kst is destroyed
-static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc)
+// Dst = Src F^-T panel by panel (gp.hpp:620, transposed) for the mc rows of Src, on c's stream and in c's phases; F: the factor of
+// context f — c itself, or another of c's device (the sparse model's Lm) — and X its compact panel inverses.  Src is destroyed.
+static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc, const gpe_ctx* f, const double* X, double* Src, double* Dst)
 {
     hipStream_t s = c->stream;
-    const int64_t N = c->N, ld = c->ld, nbo = c->nbo, ldq = b.ldq;
-    double *dKst = b.dKst, *dZt = b.dZt;
-    for (int64_t o0 = 0; o0 < N; o0 += nbo) { // gp.hpp:620, transposed
+    const int64_t N = f->N, ld = f->ld, nbo = f->nbo, ldq = b.ldq;
+    for (int64_t o0 = 0; o0 < N; o0 += nbo) {
         const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
         {
             GemmArgs g{};
-            g.C = dZt + o0 * ldq;
+            g.C = Dst + o0 * ldq;
             g.ldc = ldq;
-            g.A = dKst + o0 * ldq;
+            g.A = Src + o0 * ldq;
             g.lda = ldq;
-            g.B = b.dXp + (o0 / nbo) * (nbo * nbo);
+            g.B = X + (o0 / nbo) * (nbo * nbo);
             g.ldb = nbo;
             g.m = mc;
             g.n = pw;
@@ -105,11 +198,11 @@ static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc)
         if (oe < N) {
             GemmArgs g{};
             g.tile = b.qtile;
-            g.C = dKst + oe * ldq;
+            g.C = Src + oe * ldq;
             g.ldc = ldq;
-            g.A = dZt + o0 * ldq;
+            g.A = Dst + o0 * ldq;
             g.lda = ldq;
-            g.B = c->dA + oe + o0 * ld;
+            g.B = f->dA + oe + o0 * ld;
             g.ldb = ld;
             g.m = mc;
             g.n = N - oe;
@@ -119,34 +212,77 @@ static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc)
         }
     }
 }
-// one chunk of mc points (host, row-major): the points, Kst, kta (on the device and, kta != null, to kta[m0 + p M]) and,
-// want_z, Zt = Kst L^-T (Kst is destroyed)
-static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
-                     bool want_z)
+// Zt = Kst L^-T against the model's own factor — Kst: a chunk's cross kernel, or right-hand sides a caller put in its place (pathwise.hpp)
+static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc) { qt_forward(c, b, mc, c, b.dXp, b.dKst, b.dZt); }
+
+// The head of one chunk of mc points in either layout: the points (row-major: on the host, copied to b.dQrm, or on the device
+// already; null: none, a caller-supplied cross kernel is in b.dKst) -> SoA -> Lambda's rows (no launch for a kernel without
+// Lambda); want_ks: the cross kernel in b's layout; want_kta: kta on the device and, kta != null, to kta[m0 + p M]
+static void chunk_head(gpe_ctx* c, const QtBufs& b, const double* X, bool x_on_host, int64_t mc, bool want_ks, bool want_kta, double* kta,
+                       int64_t m0, int64_t M)
 {
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld, ldq = b.ldq;
     const int D = c->D, P = c->P;
-    double* dKst = b.dKst;
-    hipMemcpyAsync(b.dQrm, Xq_chunk, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
-    launch_transpose_x(s, b.dQrm, mc, D, b.dQt, ldq, 0);
-    project_lambda(c, s, b.dQt, ldq, 0, mc);
-    {
-        // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
+    if (X && x_on_host) {
+        hipMemcpyAsync(b.dQrm, X, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
+        X = b.dQrm;
+    }
+    if (X) {
+        launch_transpose_x(s, X, mc, D, b.dQt, ldq, 0);
+        project_lambda(c, s, b.dQt, ldq, 0, mc);
+    }
+    if (want_ks) { // gp.hpp:626-632
         PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-        launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldq); // gp.hpp:626-632
+        if (b.transposed) // k is symmetric: the cross kernel with the roles of samples and points exchanged IS the transposed block
+            launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, b.dKst, ldq);
+        else
+            launch_build_Ks(s, c->dXt, ld, N, b.dQt, ldq, mc, c->kp, b.dKst, ld);
     }
-    if (want_kta) {
-        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
-        launch_kta_t(s, dKst, ldq, N, mc, c->dAl, ld, P, b.dKta, b.mc_max, b.dPart, ldq, b.nseg); // gp.hpp:615
-        if (kta)
-            for (int p = 0; p < P; ++p)
-                hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc,
-                               hipMemcpyDeviceToHost, s);
-    }
-    if (!want_z)
+    if (!want_kta)
         return;
-    qt_forward(c, b, mc);
+    PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P); // gp.hpp:615
+    if (b.transposed)
+        launch_kta_t(s, b.dKst, ldq, N, mc, c->dAl, ld, P, b.dKta, b.mc_max, b.dPart, ldq, b.nseg);
+    else
+        launch_kta(s, b.dKst, ld, N, mc, c->dAl, ld, P, b.dKta, b.mc_max);
+    if (kta)
+        for (int p = 0; p < P; ++p)
+            hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+}
+// one chunk of the transposed layout (points on the host): its head and, want_z, Zt = Kst L^-T (Kst is destroyed)
+static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
+                     bool want_z)
+{
+    chunk_head(c, b, Xq_chunk, true, mc, true, want_kta, kta, m0, M);
+    if (want_z)
+        qt_forward(c, b, mc);
+}
+
+// K^-1 as an operand where the transposed layout does not serve (gradients, path sets): a full symmetric copy at dKi (ld x N) of
+// what ensure_inv left — its lower triangle — once per call, then per chunk Wt = Rt K^-1 (m x N, both ldt) as one product
+static void kinv_operand(gpe_ctx* c, double* dKi)
+{
+    PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+    launch_copy2d(c->stream, c->dKinv, c->ld, dKi, c->ld, c->N, c->N);
+    launch_symmetrize_from_lower(c->stream, dKi, c->ld, c->N);
+}
+static void times_kinv(gpe_ctx* c, const double* dKi, const double* dRt, double* dWt, int64_t ldt, int64_t m)
+{
+    GemmArgs g{};
+    g.C = dWt;
+    g.ldc = ldt;
+    g.A = dRt;
+    g.lda = ldt;
+    g.B = dKi;
+    g.ldb = c->ld;
+    g.m = m;
+    g.n = c->N;
+    g.k = c->N;
+    g.overwrite = 1;
+    g.tile = qt_tile(c->N);
+    PhaseScope ps(c, GPE_PH_QUERY, gemm_flops(g));
+    launch_gemm_sub(c->stream, g);
 }
 
 static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var)
@@ -154,16 +290,11 @@ static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
     hipStream_t s = c->stream;
     const int64_t N = c->N;
     const int D = c->D;
-    // chunk: two ldq x N buffers of <= 2 GiB each
-    int64_t mc_max = std::max<int64_t>(64, (((int64_t)1 << 28) / std::max<int64_t>(N, 1)) / 64 * 64);
-    mc_max = std::min<int64_t>(mc_max, round_up(M, 64));
+    const int64_t mc_max = qt_rows_per_chunk(N, M);
     QtBufs b = qt_layout(c, mc_max, N);
-    {
-        const int e = query_reserve(c, sizeof(double) * b.doubles);
-        if (e)
-            return e;
-    }
-    qt_carve(b, c->dQuery);
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b))
+        return e;
     int rc = GPE_OK;
     if (var)
         qt_panels(c, b);
@@ -182,7 +313,6 @@ static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta
         }
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }
 
@@ -235,52 +365,22 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
     // substitution runs as ONE data-flow launch (k_trsv_fwd_flow, <= GPE_MAX_P right-hand sides) instead of a
     // blocked matrix solve, whose ~2 N/64 dependent matrix-core launches are all launch floor there
     static const bool sweep_ok = env_not_zero("GPE_QUERY_SWEEP");
-    static const bool transposed_ok = env_not_zero("GPE_QUERY_T");
     const bool few = sweep_ok && c->flow_solve && M <= GPE_MAX_P && (N + NB - 1) / NB <= 256;
-    if (Xq && !few && transposed_ok && c->nbo % 128 == 0 && c->nbo <= 256 && N >= c->nbo)
+    if (Xq && !few && qt_enabled(c))
         return query_transposed(c, Xq, M, kta, var);
-    // chunk so that the N x mc cross matrix stays under ~2 GiB
-    int64_t mc_max = std::max<int64_t>(64, ((int64_t)1 << 28) / std::max<int64_t>(ld, 1));
-    mc_max = round_up(std::min<int64_t>(mc_max, round_up(M, 64)), 64);
-    if (few)
-        mc_max = GPE_MAX_P;
-    const int64_t ldq = mc_max;
-    // one allocation, carved up; kept across calls while small so that point queries do not malloc/free
-    const size_t n_qrm = (size_t)(mc_max * std::max(D, 1)), n_qt = (size_t)(ldq * std::max(xt_rows(D), 1));
-    const size_t n_ks = (size_t)(ld * mc_max), n_z = few ? n_ks : 0, n_kta = (size_t)(mc_max * P);
-    const size_t need = sizeof(double) * (n_qrm + n_qt + n_ks + n_z + n_kta + 2 * (size_t)mc_max);
-    {
-        const int e = query_reserve(c, need);
-        if (e)
-            return e;
-    }
-    double* dQrm = c->dQuery;
-    double* dQt = dQrm + n_qrm;
-    double* dKs = dQt + n_qt;
-    double* dZ = dKs + n_ks;
-    double* dKta = dZ + n_z;
-    double* dVar = dKta + n_kta;
-    double* dKvv = dVar + mc_max;
+    const int64_t mc_max = few ? GPE_MAX_P : nm_cols_per_chunk(ld, M);
+    QtBufs b = nm_layout(c, mc_max, few); // (the sweep's Z beside Ks)
+    QueryScratch qs(c);
+    if (const int e = qs.carve(b))
+        return e;
+    const int64_t ldq = b.ldq;
+    double *dQt = b.dQt, *dKs = b.dKst, *dZ = b.dZt, *dVar = b.dVar, *dKvv = b.dKvv;
     int rc = GPE_OK;
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        if (Xq) {
-            hipMemcpyAsync(dQrm, Xq + m0 * D, sizeof(double) * (size_t)(mc * D), hipMemcpyHostToDevice, s);
-            launch_transpose_x(s, dQrm, mc, D, dQt, ldq, 0);
-            project_lambda(c, s, dQt, ldq, 0, mc);
-            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-            launch_build_Ks(s, c->dXt, ld, N, dQt, ldq, mc, c->kp, dKs, ld); // gp.hpp:626-632
-        }
-        else {
+        if (!Xq) // the caller's cross kernel in the place of the device's
             copy2d_from_host(dKs, ld, KsHost + m0 * N, N, N, mc, s);
-        }
-        if (kta) {
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc * P);
-            launch_kta(s, dKs, ld, N, mc, c->dAl, ld, P, dKta, mc_max); // gp.hpp:615
-            for (int p = 0; p < P; ++p)
-                hipMemcpyAsync(kta + m0 + (int64_t)p * M, dKta + (int64_t)p * mc_max, sizeof(double) * (size_t)mc,
-                               hipMemcpyDeviceToHost, s);
-        }
+        chunk_head(c, b, Xq ? Xq + m0 * D : nullptr, true, mc, Xq != nullptr, kta != nullptr, kta, m0, M);
         if (var) {
             const double* Z = dKs;
             if (few) {
@@ -314,6 +414,5 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
         }
     }
     drain_phases(c);
-    query_release(c);
     return rc;
 }

@@ -61,78 +61,23 @@ bool sp_use_gram_kernel(int64_t M, int cus)
     return nt * (nt + 1) / 2 < 2 * (int64_t)cus;
 }
 
-// the two layouts of a chunk (query.hpp): transposed — points contiguous, from one outer panel of pseudo-inputs on — or N x M
-bool sp_transposed(const gpe_ctx* c) { return c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo; }
+// the layout of a chunk (query.hpp): transposed — points contiguous, from one outer panel of pseudo-inputs on — or N x M with
+// room for a weighted copy beside Ks
+QtBufs sp_layout(const gpe_ctx* c, int64_t mc_max) { return qt_serves(c) ? qt_layout(c, mc_max, c->N) : nm_layout(c, mc_max, true); }
 
-QtBufs sp_layout(const gpe_ctx* c, int64_t mc_max, bool transposed)
-{
-    QtBufs b = qt_layout(c, mc_max, c->N);
-    if (!transposed) { // Kst holds Ks (ld x mc_max, k-contiguous columns), solved in place; Zt: room for a weighted copy
-        b.ldq = mc_max;
-        b.n_qt = (size_t)(b.ldq * std::max(xt_rows(c->D), 1));
-        b.n_kst = (size_t)(c->ld * mc_max);
-        b.n_zt = b.n_kst;
-        b.n_xp = 0;
-        b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_part + b.n_kta + 2 * (size_t)mc_max;
-    }
-    return b;
-}
-
-// Dst = Src F^-T panel by panel for the factor F of context f (X: its compact panel inverses), transposed layout; Src is destroyed.
-// The loop of qt_chunk (query.hpp; gp.hpp:620 transposed) with the factor as an argument: lst against L, lmst against Lm.
-void sp_solve_t(gpe_ctx* run, const gpe_ctx* f, const double* X, double* Src, double* Dst, int64_t ldq, int64_t mc, int qtile)
-{
-    hipStream_t s = run->stream;
-    const int64_t N = f->N, ld = f->ld, nbo = f->nbo;
-    for (int64_t o0 = 0; o0 < N; o0 += nbo) {
-        const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
-        {
-            GemmArgs g{};
-            g.C = Dst + o0 * ldq;
-            g.ldc = ldq;
-            g.A = Src + o0 * ldq;
-            g.lda = ldq;
-            g.B = X + (o0 / nbo) * (nbo * nbo);
-            g.ldb = nbo;
-            g.m = mc;
-            g.n = pw;
-            g.k = pw;
-            g.overwrite = 1;
-            g.tile = qtile;
-            launch_gemm_sub(s, g);
-        }
-        if (oe < N) {
-            GemmArgs g{};
-            g.tile = qtile;
-            g.C = Src + oe * ldq;
-            g.ldc = ldq;
-            g.A = Dst + o0 * ldq;
-            g.lda = ldq;
-            g.B = f->dA + oe + o0 * ld;
-            g.ldb = ld;
-            g.m = mc;
-            g.n = N - oe;
-            g.k = pw;
-            launch_gemm_sub(s, g);
-        }
-    }
-}
-
-// the chunk's points (device, row-major mc x D) -> SoA, the cross kernel against the pseudo-inputs, V by the inner model's factor.
-// Returns V's place: element (n, i) at Z[n sn + i si].
-const double* sp_v_chunk(gpe_sp_ctx* h, const QtBufs& b, bool transposed, const double* dXrm, int64_t mc, int64_t* sn, int64_t* si)
+// the chunk's points (device, row-major mc x D) -> SoA, the cross kernel against the pseudo-inputs (spgp.hpp:396 / :597), V by the
+// inner model's factor (:398 / :598) — a chunk of the batched query with the inner model as the model.  Its phases record nothing:
+// the inner context's profiling is never on.  Returns V's place: element (n, i) at Z[n sn + i si].
+const double* sp_v_chunk(gpe_sp_ctx* h, const QtBufs& b, const double* dXrm, int64_t mc, int64_t* sn, int64_t* si)
 {
     gpe_ctx* c = h->in;
-    hipStream_t s = c->stream;
-    launch_transpose_x(s, dXrm, mc, c->D, b.dQt, b.ldq, 0);
-    if (transposed) {
-        launch_build_Ks(s, b.dQt, b.ldq, mc, c->dXt, c->ld, c->N, c->kp, b.dKst, b.ldq); // spgp.hpp:396 / :597, transposed
-        sp_solve_t(c, c, b.dXp, b.dKst, b.dZt, b.ldq, mc, b.qtile);                      // :398 / :598
+    chunk_head(c, b, dXrm, false, mc, true, false, nullptr, 0, 0);
+    if (b.transposed) {
+        qt_forward(c, b, mc);
         *sn = 1;
         *si = b.ldq;
         return b.dZt;
     }
-    launch_build_Ks(s, c->dXt, c->ld, c->N, b.dQt, b.ldq, mc, c->kp, b.dKst, c->ld);
     trsm_left_blocked(c, c->dA, b.dKst, c->ld, c->N, mc, false, GPE_PH_QUERY);
     *sn = c->ld;
     *si = 1;
@@ -149,10 +94,6 @@ int sp_scratch(gpe_sp_ctx* h)
     }
     return GPE_OK;
 }
-
-struct SpMarks { // event pairs of one phase over all chunks (profiling only)
-    std::vector<hipEvent_t> ev[3];
-};
 
 int sp_compute_locked(gpe_sp_ctx* h)
 {
@@ -187,18 +128,15 @@ int sp_compute_locked(gpe_sp_ctx* h)
     hipStream_t s = in->stream;
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, in->device);
-    const bool transposed = sp_transposed(in);
     const int64_t chunk = sp_chunk(M, N);
     const bool own_gram = sp_use_gram_kernel(M, cus);
-    QtBufs b = sp_layout(in, chunk, transposed);
-    {
-        const int e = query_reserve(in, sizeof(double) * b.doubles);
-        if (e) {
-            h->err = "sparse GP: " + in->err;
-            return e;
-        }
+    QtBufs b = sp_layout(in, chunk);
+    const bool transposed = b.transposed;
+    QueryScratch qs(in);
+    if (const int e = qs.carve(b)) {
+        h->err = "sparse GP: " + in->err;
+        return e;
     }
-    qt_carve(b, in->dQuery);
     const int64_t Mpad = h->Mpad, pstride = Mpad * Mpad;
     const int S0 = sparse_gram_slices(M, std::min(chunk, N), cus); // (the first chunk is the longest: no chunk has more slices)
     std::vector<int64_t> plan;
@@ -219,27 +157,20 @@ int sp_compute_locked(gpe_sp_ctx* h)
         launch_zero2d(s, dA, lda, Mpad, Mpad);
     if (transposed)
         qt_panels(in, b);
-    SpMarks mk;
-    auto mark = [&](int ph) {
-        if (h->prof) {
-            hipEvent_t e = get_event(in);
-            hipEventRecord(e, s);
-            mk.ev[ph].push_back(e);
-        }
-    };
+    Marks mk(in->pool, s, h->prof); // per chunk three phases — V, ep and r, the Gram — of two boundaries each
     const int64_t nt = (M + 63) / 64, tiles = nt * (nt + 1) / 2;
     int64_t row0 = 0, slot0 = 0;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, N - n0);
         int64_t sn = 0, si = 0;
-        mark(0);
-        const double* Z = sp_v_chunk(h, b, transposed, h->dX + n0 * D, mc, &sn, &si);
-        mark(0);
-        mark(1);
+        mk.mark();
+        const double* Z = sp_v_chunk(h, b, h->dX + n0 * D, mc, &sn, &si);
+        mk.mark();
+        mk.mark();
         launch_sp_ep(s, Z, sn, si, mc, M, h->c, h->sig, h->dEp + n0, h->dW);
         launch_sp_r(s, Z, sn, si, mc, M, h->dW, h->dY + n0, N, P, sc->dOm, sc->ld);
-        mark(1);
-        mark(2);
+        mk.mark();
+        mk.mark();
         if (own_gram) {
             const int S = sparse_gram_slices(M, mc, cus);
             const int64_t rows = tiles * S;
@@ -269,7 +200,7 @@ int sp_compute_locked(gpe_sp_ctx* h)
             g.overwrite = 2;
             launch_gemm_sub(s, g);
         }
-        mark(2);
+        mk.mark();
     }
     launch_sp_diag_add(s, dA, lda, M, h->sig); // spgp.hpp:405: sig I + V V^T
     launch_symmetrize_from_lower(s, dA, lda, M);
@@ -280,20 +211,13 @@ int sp_compute_locked(gpe_sp_ctx* h)
         h->err = "sparse GP: stream sync failed";
         return GPE_ERR_HIP;
     }
-    if (h->prof) {
+    if (h->prof)
         for (int ph = 0; ph < 3; ++ph) {
-            double tot = 0.0;
-            for (size_t q = 0; q + 1 < mk.ev[ph].size(); q += 2) {
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, mk.ev[ph][q], mk.ev[ph][q + 1]);
-                tot += ms;
-            }
-            h->ms[ph] = tot;
-            for (hipEvent_t e : mk.ev[ph])
-                in->pool.push_back(e);
+            h->ms[ph] = 0.0;
+            for (int q = 2 * ph; q + 1 < mk.count(); q += 6)
+                h->ms[ph] += mk.ms(q, q + 1);
         }
-    }
-    query_release(in);
+    qs.release();
     // Lm = chol(A) and bet = Lm^-1 r in the scratch context (A and r are complete: the stream has been waited for)
     int rc;
     {
@@ -335,32 +259,25 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     hipStream_t s = in->stream;
     const int64_t M = h->M, Mpad = h->Mpad;
     const int D = h->D, P = h->P;
-    const bool transposed = sp_transposed(in);
     // points per chunk: from M alone (a prediction must not depend on the batch around it)
     const int64_t mc_max = std::min<int64_t>(sparse_default_chunk(M), 16384);
-    QtBufs b = sp_layout(in, mc_max, transposed);
+    QtBufs b = sp_layout(in, mc_max);
+    const bool transposed = b.transposed;
     // behind the query buffers: v1, v2, zero (mc_max each), mu (mc_max x P), s2, the partial sums of the P outputs
     const size_t n_extra = 4 * (size_t)mc_max + (size_t)mc_max * P + (size_t)b.nseg * P * (size_t)b.ldq;
-    {
-        const int e = query_reserve(in, sizeof(double) * (b.doubles + n_extra));
-        if (e) {
-            h->err = "sparse GP: " + in->err;
-            return e;
-        }
+    QueryScratch qs(in);
+    if (const int e = qs.carve(b, n_extra)) {
+        h->err = "sparse GP: " + in->err;
+        return e;
     }
-    qt_carve(b, in->dQuery);
     double* dV1 = b.dKvv + b.mc_max;
     double* dV2 = dV1 + mc_max;
     double* dZero = dV2 + mc_max;
     double* dS2 = dZero + mc_max;
     double* dMu = dS2 + mc_max;
     double* dPartP = dMu + (size_t)mc_max * P;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        e0 = get_event(in);
-        e1 = get_event(in);
-        hipEventRecord(e0, s);
-    }
+    Marks mk(in->pool, s, h->prof);
+    mk.mark();
     HIPCHK(h, hipMemsetAsync(dZero, 0, sizeof(double) * (size_t)mc_max, s));
     if (transposed) {
         qt_panels(in, b);
@@ -373,12 +290,12 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
         const int64_t tc = std::min<int64_t>(mc_max, T - t0);
         int64_t sn = 0, si = 0;
         HIPCHK(h, hipMemcpyAsync(b.dQrm, Xt + t0 * D, sizeof(double) * (size_t)(tc * D), hipMemcpyHostToDevice, s));
-        const double* Z = sp_v_chunk(h, b, transposed, b.dQrm, tc, &sn, &si); // lst (spgp.hpp:597-598)
+        const double* Z = sp_v_chunk(h, b, b.dQrm, tc, &sn, &si); // lst (spgp.hpp:597-598)
         launch_kvv(s, b.dQt, b.ldq, tc, in->kp, b.dKvv);                      // _k_diag (:630-634)
         hipStream_t s2nd = s;
         if (transposed) {
             launch_row_var_t(s, Z, b.ldq, M, tc, b.dKvv, dV1, b.dPart, b.ldq, b.nseg);   // c - |lst|^2
-            sp_solve_t(in, sc, h->dXp2, b.dZt, b.dKst, b.ldq, tc, b.qtile);              // lmst (:599), into Kst
+            qt_forward(in, b, tc, sc, h->dXp2, b.dZt, b.dKst);                           // lmst (:599), into Kst
             launch_row_var_t(s, b.dKst, b.ldq, M, tc, dZero, dV2, b.dPart, b.ldq, b.nseg); // - |lmst|^2
             if (mu)
                 launch_kta_t(s, b.dKst, b.ldq, M, tc, h->dBet, Mpad, P, dMu, mc_max, dPartP, b.ldq, b.nseg); // :604
@@ -409,16 +326,9 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     }
     if (rc != GPE_OK)
         h->err = "sparse GP: predict: stream sync failed";
-    if (h->prof) {
-        hipEventRecord(e1, s);
-        float ms = 0.f;
-        if (hipEventSynchronize(e1) == hipSuccess)
-            hipEventElapsedTime(&ms, e0, e1);
-        h->ms[4] = ms;
-        in->pool.push_back(e0);
-        in->pool.push_back(e1);
-    }
-    query_release(in);
+    mk.mark();
+    if (h->prof)
+        h->ms[4] = mk.ms(0, 1);
     return rc;
 }
 

@@ -112,18 +112,12 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
             HIPCHK(h, h->dPart.reserve((size_t)(SG0 * pstride)));
         HIPCHK(h, hipMemcpyAsync(h->dPlan, plan.data(), sizeof(int64_t) * plan.size(), hipMemcpyHostToDevice, s));
     }
-    std::vector<hipEvent_t> ev[5];
+    // two boundaries around the M x M part, per chunk two around each of its three phases, two around the finish
+    Marks mk(in->pool, s, h->prof);
     hipEvent_t ev_order[2] = {nullptr, nullptr};
-    auto mark = [&](int ph) {
-        if (h->prof) {
-            hipEvent_t e = get_event(in);
-            hipEventRecord(e, s);
-            ev[ph].push_back(e);
-        }
-    };
     // ---- M x M: Li = L^-1, invQ = Li^T Li; Lmi = Lm^-1; Lti = Lm^-1 Li = (L Lm)^-1, invA = Lti^T Lti (spgp.hpp:501-505), b1 = Lti^T bet
     // (:507); Li^T and Lti^T as matrices of their own: the chunk's products want both operands contiguous along their non-k index
-    mark(0);
+    mk.mark();
     HIPCHK(h, hipMemsetAsync(b.Wl, 0, sizeof(double) * (size_t)(7 * Mq * Mq), s)); // Wl, IQm, IAm, TT, LiT, LtiT, Lmi
     HIPCHK(h, hipMemsetAsync(b.Kt, 0, sizeof(double) * (size_t)(4 * ldq * Mq), s)); // Kt, B1t, IQt, ILVt
     launch_set_identity(s, b.Wl, Mq, M);
@@ -146,29 +140,25 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
     sp_grad_lauum(s, b.Wl, b.IAm, Mq, M);
     launch_sp_gtrans(s, b.Wl, b.LtiT, Mq, M);
     launch_sp_gb1(s, b.Wl, Mq, M, h->dBet, Mpad, P, b.b1, Mq);
-    mark(0);
+    mk.mark();
     // ---- the pass over N.  V of a chunk comes from the model's own path (sp_v_chunk: the cross kernel and the solve exactly as
     // gpe_sp_compute ran them): ep, Lm and bet were formed from THAT V, and the gradient's large terms cancel only against a V that
     // is consistent with them — K~ through explicit inverses instead lost three digits at M = 1024 (cond K_mm 7e7).
-    const bool transposed = sp_transposed(in);
-    QtBufs bq = sp_layout(in, chunk, transposed);
-    {
-        const int e = query_reserve(in, sizeof(double) * bq.doubles);
-        if (e) {
-            h->err = "sparse GP gradient: " + in->err;
-            return e;
-        }
+    QtBufs bq = sp_layout(in, chunk);
+    QueryScratch qs(in);
+    if (const int e = qs.carve(bq)) {
+        h->err = "sparse GP gradient: " + in->err;
+        return e;
     }
-    qt_carve(bq, in->dQuery);
-    if (transposed)
+    if (bq.transposed)
         qt_panels(in, bq);
     const int64_t nt = (M + 63) / 64, tiles = nt * (nt + 1) / 2;
     int64_t row0 = 0, slot0 = 0, blk0 = 0;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, N - n0);
-        mark(1);
+        mk.mark();
         int64_t sn = 0, si = 0;
-        const double* Z = sp_v_chunk(h, bq, transposed, h->dX + n0 * D, mc, &sn, &si); // V (:396-398)
+        const double* Z = sp_v_chunk(h, bq, h->dX + n0 * D, mc, &sn, &si); // V (:396-398)
         launch_sp_grs(s, h->dEp + n0, mc, b.rs);
         launch_sp_gvt(s, Z, sn, si, mc, M, b.rs, b.B1t, ldq); // V~^T (:401), for now where B1t will be
         for (int q = 0; q < 3; ++q) { // ILVt = V~t Lm^-T (:483), IQt = V~t L^-1 (:504 invLV), B1t = ILVt Lt^-1 (:502)
@@ -188,15 +178,15 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
         launch_transpose_x(s, h->dX + n0 * D, mc, D, b.Qt, ldq, 0);
         launch_build_Ks(s, b.Qt, ldq, mc, in->dXt, in->ld, M, in->kp, b.Kt, ldq); // K(Xb, X)^T (:396), transposed layout
         launch_sp_scale(s, b.Kt, 1, ldq, mc, M, b.rs, b.Kt); // K~ (:400)
-        mark(1);
-        mark(2);
+        mk.mark();
+        mk.mark();
         launch_sp_gcol(s, b.ILVt, b.IQt, ldq, mc, M, h->dBet, Mpad, P, h->dY + n0, N, h->dEp + n0, b.rs, h->c, h->sig, h->jitter, b.big, b.R,
                        b.part + 3 * blk0);
         blk0 += (mc + 63) / 64;
         launch_sp_grow(s, b.Kt, b.B1t, b.IQt, ldq, mc, M, b.b1, Mq, P, b.big, b.R, b.Qt, in->kp, h->sig, sparse_grad_row_slices(M, mc, cus), b.Rpart,
                        Mq, n0 == 0 ? 1 : 0, b.Racc);
-        mark(2);
-        mark(3);
+        mk.mark();
+        mk.mark();
         if (own_gram) { // TT += IQ diag(bigsum) IQ^T (:518): the model's Gram kernel, signed weights
             const int S = sparse_gram_slices(M, mc, cus);
             const int64_t rows = tiles * S;
@@ -224,36 +214,33 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
             g.overwrite = 2;
             launch_gemm_sub(s, g);
         }
-        mark(3);
+        mk.mark();
     }
-    mark(4);
+    mk.mark();
     launch_symmetrize_from_lower(s, b.TT, Mq, M);
     launch_sp_gfinish(s, in->dXt, in->ld, in->kp, M, P, b.b1, Mq, b.IQm, b.IAm, b.TT, Mq, b.Racc, h->sig, h->jitter, b.part, blk0, b.dxb, b.tb, b.cs,
                       b.dhp);
-    mark(4);
+    mk.mark();
     std::vector<double> hxb((size_t)(M * D)), hhp((size_t)D + 2);
     HIPCHK(h, hipMemcpyAsync(hxb.data(), b.dxb, sizeof(double) * hxb.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipMemcpyAsync(hhp.data(), b.dhp, sizeof(double) * hhp.size(), hipMemcpyDeviceToHost, s));
     const bool sync_ok = hipStreamSynchronize(s) == hipSuccess && hipGetLastError() == hipSuccess;
-    query_release(in);
+    in->pool.push_back(ev_order[0]);
+    in->pool.push_back(ev_order[1]);
     if (!sync_ok) {
         h->err = "sparse GP gradient: stream sync failed";
         return GPE_ERR_HIP;
     }
-    in->pool.push_back(ev_order[0]);
-    in->pool.push_back(ev_order[1]);
-    if (h->prof)
-        for (int ph = 0; ph < 5; ++ph) {
-            double tot = 0.0;
-            for (size_t q = 0; q + 1 < ev[ph].size(); q += 2) {
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, ev[ph][q], ev[ph][q + 1]);
-                tot += ms;
-            }
-            h->gms[ph] = tot;
-            for (hipEvent_t e : ev[ph])
-                in->pool.push_back(e);
-        }
+    if (h->prof) {
+        const int n = mk.count();
+        for (double& ms : h->gms)
+            ms = 0.0;
+        h->gms[0] = mk.ms(0, 1);
+        for (int q = 2; q + 5 < n - 2; q += 6) // (the chunks' six boundaries each, between the first two and the last two)
+            for (int ph = 1; ph <= 3; ++ph)
+                h->gms[ph] += mk.ms(q + 2 * ph - 2, q + 2 * ph - 1);
+        h->gms[4] = mk.ms(n - 2, n - 1);
+    }
     if (d_xb)
         memcpy(d_xb, hxb.data(), sizeof(double) * hxb.size());
     memcpy(d_hp, hhp.data(), sizeof(double) * hhp.size());

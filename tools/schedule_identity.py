@@ -13,6 +13,9 @@ tril(get_L()) and of get_alpha(), and the bits of log_lik().  D = 4, SE-ARD, noi
 
 The case `lifecycle` is about the handle's memory instead of the schedule: one handle through every event that allocates, grows,
 drops or hands on a device buffer (lifecycle_steps); it prints the sha256 of every array returned and the bits of every scalar.
+
+The cases of QUERY_CASES and SPARSE_CASES are about the host side of the query family (limbo_amd/csrc/query.hpp and the calls
+built on its chunk helpers): one line per call with its launches and the sha256 of every array it returned.
 """
 import argparse
 import hashlib
@@ -53,6 +56,29 @@ CASES = {
     "w": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_LOOKAHEAD": "0"}, "single stream in the panels"),
 }
 CASES["lifecycle"] = (300, 2, {}, "one handle through set_data, grow, the query scratch's give-back, a change of P, clone and destroy")
+# The query family (limbo_amd/csrc/query.hpp and the calls built on its chunk helpers): a fitted model (P = 2) through query_batch,
+# query_batch_cross, query_batch_grad, joint_query, joint_draws, a path set, add_samples + a query.  One line per call: its
+# launches and the sha256 of every array it returned.  case: (N, points, Lambda columns, profiling, environment, what it reaches)
+QUERY_CASES = {
+    "q64": (520, 70, 0, False, {}, "the transposed layout, 64-tiles, ragged in N and in the points"),
+    "q128": (1100, 70, 0, False, {}, "the transposed layout, 128-tiles"),
+    "qnbo": (520, 70, 0, False, {"GPE_NBO": "192"}, "a panel width the transposed layout does not serve: N x M, the by-inverse routes"),
+    "qnm": (520, 70, 0, False, {"GPE_QUERY_T": "0"}, "N x M by the switch; the joint posterior stays transposed"),
+    "qsub": (200, 70, 0, False, {"GPE_SMALL": "0"}, "fewer samples than one outer panel: N x M"),
+    "qfew": (520, 5, 0, False, {}, "a handful of points: the one-launch sweep of query_impl"),
+    "qlam": (520, 70, 1, False, {}, "SE-ARD with one Lambda column: project_lambda launches"),
+    "qprof": (520, 70, 0, True, {}, "profiling on: the timers' branches"),
+    "qprofnm": (520, 70, 0, True, {"GPE_QUERY_T": "0"}, "profiling on in the N x M layout"),
+}
+# The sparse model: sp_compute, sp_predict, sp_grad, with sp_set_profiling off and on (the *_phase_ms values are times: printed as
+# "finite and >= 0" only).  case: (N, pseudo-inputs, points, environment, what it reaches)
+SPARSE_CASES = {
+    "s130": (1300, 130, 130, {}, "fewer pseudo-inputs than one outer panel: N x M, one chunk"),
+    "s130c": (1300, 130, 130, {"GPE_SPARSE_CHUNK": "512"}, "... three chunks, ragged last"),
+    "s300": (1300, 300, 130, {}, "the transposed layout: both panel solves of the prediction"),
+    "s300c": (1300, 300, 130, {"GPE_SPARSE_CHUNK": "512", "GPE_QUERY_T": "0"}, "... three chunks; transposed whatever GPE_QUERY_T says"),
+}
+ALL_CASES = {**CASES, **QUERY_CASES, **SPARSE_CASES}
 D = 4
 NOISE = 0.01
 CHILD_TIMEOUT_S = 180
@@ -135,6 +161,101 @@ def run_lifecycle(np, _capi):
     print(json.dumps(out), flush=True)
 
 
+def traced(lib, call):
+    """(what `call` returned, the launches it made: [stream index, kernel, grid, block] each)"""
+    with tempfile.TemporaryDirectory() as tmp:
+        path = Path(tmp) / "trace.txt"
+        try:
+            assert lib.fn("trace")(1) == 0
+            res = call()
+            assert lib.fn("trace_dump")(str(path).encode()) == 0
+        finally:
+            lib.fn("trace")(0)
+        lines = path.read_text().splitlines()
+    recs = [_TRACE_LINE.match(ln) for ln in lines]
+    assert lines and all(recs), lines[:3]
+    return res, [[int(m[1]), m[2], [int(m[3]), int(m[4]), int(m[5])], int(m[6])] for m in recs]
+
+
+def report(np, case, label, launches, arrays, times=None):
+    """one line: a call's launches, the sha256 of its arrays (None: not asked for) and — times — whether they are finite and >= 0"""
+    sha = lambda a: None if a is None else hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    out = {"case": case, "call": label, "launches": launches, "sha256": {k: sha(v) for k, v in arrays.items()}}
+    if times is not None:
+        out["times_finite_nonneg"] = {k: bool(np.isfinite(v) and v >= 0.0) for k, v in times.items()}
+    print(json.dumps(out), flush=True)
+
+
+def run_query_case(np, _capi, name):
+    N, M, lam, prof, _, _ = QUERY_CASES[name]
+    P, S, R, q_new = 2, 3, 64, 40
+    lib = _capi.load_engine()
+    X, Y = problem(np, N + q_new, P, 3000)
+    rng = np.random.default_rng(3001)
+    Xq = rng.uniform(-2.0, 2.0, (M, D))
+    theta = np.concatenate([0.1 * np.arange(D) - 0.2, 0.3 * rng.standard_normal(D * lam), [0.2]])
+    h = _capi.Handle(lib, 0)
+    h.set_data(X[:N], Y[:N])
+    h.set_kernel(_capi.KERNEL_SE_ARD, theta, NOISE)
+    h.set_profiling(prof)
+    assert h.compute() == 0
+
+    def call(label, fn, names, times=None):
+        res, launches = traced(lib, fn)
+        report(np, name, label, launches, dict(zip(names, res)), times() if times and prof else None)
+
+    call("query_batch", lambda: h.query_batch(Xq), ("kta", "var"))
+    call("query_batch.kta", lambda: h.query_batch(Xq, want_var=False), ("kta", "var"))
+    call("query_batch.var", lambda: h.query_batch(Xq, want_mu=False), ("kta", "var"))
+
+    def cross():  # a caller-supplied cross kernel: N x M, column-major
+        Ks = np.asfortranarray(np.exp(-0.5 * ((X[:N, None, :] - Xq[None, :, :]) ** 2).sum(axis=2)))
+        kta, zz = np.zeros((M, P), order="F"), np.zeros(M)
+        dp = lambda a: a.ctypes.data_as(_capi._dp)
+        assert lib.fn("query_batch_cross")(h._h, dp(Ks), M, dp(kta), dp(zz)) == 0
+        return kta, zz
+
+    call("query_batch_cross", cross, ("kta", "zz"))
+    grad_names = ("kta", "var", "dkta", "dvar")
+    call("query_batch_grad", lambda: h.query_batch_grad(Xq), grad_names, h.query_grad_phase_ms)
+    call("query_batch_grad.dkta", lambda: h.query_batch_grad(Xq, want=("dkta",)), grad_names, h.query_grad_phase_ms)
+    call("joint_query", lambda: h.joint_query(Xq, 1e-6), ("kta", "cov"), h.joint_phase_ms)
+    Z = rng.standard_normal((M, S, P))
+    call("joint_draws", lambda: h.joint_draws(Xq, Z, 1e-6), ("status", "F", "argmax", "fmax"), h.joint_phase_ms)
+    Om, ph = rng.standard_normal((R, D + lam)), rng.uniform(0.0, 2.0 * np.pi, R)
+    W, E = rng.standard_normal((R, S, P)), rng.standard_normal((N, S, P))
+    paths = []
+    call("paths_create", lambda: paths.append(h.paths(R, S, Om, ph, W, E)) or (), (), lambda: paths[0].phase_ms())
+    call("paths_eval", lambda: paths[0].eval(Xq), ("F", "dF"), lambda: paths[0].phase_ms())
+    call("paths_argmax", lambda: paths[0].argmax(Xq), ("argmax", "fmax"), lambda: paths[0].phase_ms())
+    paths[0].close()
+    call("add_samples", lambda: (h.add_samples(X[N:], Y), h.get_alpha()), ("status", "alpha"))
+    call("add_samples.query_batch", lambda: h.query_batch(Xq), ("kta", "var"))
+    h.close()
+
+
+def run_sparse_case(np, _capi, name):
+    N, M, T, _, _ = SPARSE_CASES[name]
+    lib = _capi.load_engine()
+    X, Y = problem(np, N, 2, 4000)
+    Xt = np.random.default_rng(4001).uniform(-2.0, 2.0, (T, D))
+    for prof in (False, True):
+        h = _capi.SparseHandle(lib, 0)
+        h.set_data(X, Y)
+        h.set_pseudo(X[:: N // M][:M])
+        h.set_hparams(0.1 * np.arange(D) - 0.2, 0.1, np.log(NOISE), 1e-6)
+        h.set_profiling(prof)
+        tag = ".prof" if prof else ""
+        st, launches = traced(lib, h.compute)
+        report(np, name, "sp_compute" + tag, launches, {"status": st, "nlml": h.nlml(), "bet": h.get_bet(), "ep": h.get_ep(), "Lm": np.tril(h.get_Lm())},
+               h.phase_ms() if prof else None)
+        (mu, s2), launches = traced(lib, lambda: h.predict(Xt))
+        report(np, name, "sp_predict" + tag, launches, {"mu": mu, "s2": s2}, h.phase_ms() if prof else None)
+        (st, gx, gh), launches = traced(lib, h.grad)
+        report(np, name, "sp_grad" + tag, launches, {"status": st, "d_xb": gx, "d_hp": gh}, h.grad_phase_ms() if prof else None)
+        h.close()
+
+
 def run_case(name, root):
     sys.path.insert(0, str(root))
     import numpy as np
@@ -144,6 +265,10 @@ def run_case(name, root):
     assert Path(_capi.__file__).resolve().is_relative_to(root), _capi.__file__
     if name == "lifecycle":
         return run_lifecycle(np, _capi)
+    if name in QUERY_CASES:
+        return run_query_case(np, _capi, name)
+    if name in SPARSE_CASES:
+        return run_sparse_case(np, _capi, name)
     N, P, _, _ = CASES[name]
     lib = _capi.load_engine()
     hs = []
@@ -160,23 +285,13 @@ def run_case(name, root):
         assert all(s == 0 for s in st), st
 
     evaluate()
-    with tempfile.TemporaryDirectory() as tmp:
-        path = Path(tmp) / "trace.txt"
-        try:
-            assert lib.fn("trace")(1) == 0
-            evaluate()
-            assert lib.fn("trace_dump")(str(path).encode()) == 0
-        finally:
-            lib.fn("trace")(0)
-        lines = path.read_text().splitlines()
-    recs = [_TRACE_LINE.match(ln) for ln in lines]
-    assert lines and all(recs), lines[:3]
+    _, launches = traced(lib, evaluate)
     sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
     out = {
         "case": name,
         "N": N,
         "P": P,
-        "launches": [[int(m[1]), m[2], [int(m[3]), int(m[4]), int(m[5])], int(m[6])] for m in recs],
+        "launches": launches,
         "L_sha256": [sha(np.tril(h.get_L())) for h in hs],
         "alpha_sha256": [sha(h.get_alpha()) for h in hs],
         "log_lik_bits": [struct.pack(">d", h.log_lik()).hex() for h in hs],
@@ -186,27 +301,60 @@ def run_case(name, root):
     print(json.dumps(out), flush=True)
 
 
+def compact(rec, kernels, seen):
+    """A per-call line as it is printed: every launch as kernel index:grid[:block][@stream] (the grid without its trailing ones,
+    the block unless it is 256, the stream index unless it is 0, `*n` behind a launch repeated n times in a row), the hashes cut to
+    16 digits.  Nothing of the sequence is lost."""
+    runs = []
+    for s, k, grid, block in rec["launches"]:
+        while len(grid) > 1 and grid[-1] == 1:
+            grid = grid[:-1]
+        e = f"{kernels.setdefault(k, len(kernels))}:{','.join(map(str, grid))}" + (f":{block}" if block != 256 else "") + (f"@{s}" if s else "")
+        if runs and runs[-1][0] == e:
+            runs[-1][1] += 1
+        else:
+            runs.append([e, 1])
+    seq = " ".join(e if n == 1 else f"{e}*{n}" for e, n in runs)
+    first = seen.setdefault(seq, f"{rec['case']}/{rec['call']}")  # a sequence printed before: "= the call that made it first"
+    rec["launches"] = seq if first == f"{rec['case']}/{rec['call']}" else "= " + first
+    rec["sha256"] = {k: v and v[:16] for k, v in rec["sha256"].items()}
+    if "times_finite_nonneg" in rec:
+        rec["times_finite_nonneg"] = all(rec["times_finite_nonneg"].values())
+    return json.dumps(rec, separators=(",", ":"))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--root", default=str(Path(__file__).resolve().parent.parent))
-    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--cases", default=",".join(ALL_CASES))
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
     root = Path(a.root).resolve()
     if a.child:
         run_case(a.child, root)
         return 0
+    kernels = {}  # (the per-call lines name their kernels by index into this table, printed last)
+    seen = {}
+    status = 0
     for name in a.cases.split(","):
         env = {k: v for k, v in os.environ.items() if not k.startswith("GPE_")}
-        env.update(CASES[name][2])
+        env.update(ALL_CASES[name][-2])
+        per_call = name not in CASES
         try:
-            rc = subprocess.run([sys.executable, __file__, "--root", str(root), "--child", name], env=env, timeout=CHILD_TIMEOUT_S).returncode
+            r = subprocess.run([sys.executable, __file__, "--root", str(root), "--child", name], env=env, timeout=CHILD_TIMEOUT_S,
+                               stdout=subprocess.PIPE if per_call else None, text=True)
+            rc = r.returncode
+            for ln in (r.stdout or "").splitlines():
+                print(compact(json.loads(ln), kernels, seen), flush=True)
         except subprocess.TimeoutExpired:
             rc = 124
         if rc != 0:
             print(f"case {name}: the child ended with status {rc}; stopping", file=sys.stderr)
-            return 1
-    return 0
+            status = 1
+            break
+    if kernels:
+        print(json.dumps({"kernels": list(kernels)}), flush=True)
+    return status
 
 
 if __name__ == "__main__":
