@@ -7,6 +7,7 @@
 // thompson_paths_batch: the same proposals from draws that are FUNCTIONS (model::GP::sample_paths, include/gpe_pathwise.h): each of
 // the q paths is maximised over [0, 1]^D by a candidate cloud followed by a lock-step gradient search on the path itself — no
 // candidate set to keep resident, no M x M covariance, and the maximum is found, not only its basin.
+// Deterministic batches from the same model state (GP-BUCB, the kriging believer): acqui/batch_select.hpp.
 #ifndef LIMBO_AMD_ACQUI_THOMPSON_HPP
 #define LIMBO_AMD_ACQUI_THOMPSON_HPP
 #include <algorithm>

@@ -65,6 +65,7 @@
 #include "../../../gpe_joint.h"
 #include "../../../gpe_append.h"
 #include "../../../gpe_query_grad.h"
+#include "../../../gpe_batch_select.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -449,6 +450,50 @@ namespace limbo {
                 argmax.assign((size_t)(n_draws * _dim_out), 0);
                 fmax.assign((size_t)(n_draws * _dim_out), 0.0);
                 _draws(points, Z, n_draws, jitter, nullptr, argmax.data(), fmax.data());
+            }
+
+            /// Addition (include/gpe_batch_select.h): q greedy picks among `points` from ONE model state — take the maximiser of
+            /// the score, condition the posterior variance on a hallucinated observation of noise obs_noise there (the mean stays),
+            /// take the next (GP-BUCB, kriging believer, max-variance design; acqui/batch_select.hpp wraps the first two).
+            /// rule: GPE_SELECT_UCB (param = beta), GPE_SELECT_EI (param = f+ + jitter) or GPE_SELECT_VAR.  mu: one COMPLETE value
+            /// per point (mean functor and aggregator applied by the caller), or empty: k(X, v)^T alpha of output 0 with no mean
+            /// functor.  var_add is added to the clamped variance in the score (the kernel's noise for what query() reports).
+            /// idx / score: the pick and its score per round.  Returns 0, or t + 1 when round t's pivot is not positive: idx and
+            /// score then end with round t.  On the model's home device; no samples (the prior), a host-resident model below the
+            /// batch crossover and kernels without device code: on the host from the M x M covariance of query_joint.
+            int select_batch(const std::vector<Eigen::VectorXd>& points, int q, int rule, double param, const std::vector<double>& mu,
+                double var_add, double obs_noise, bool distinct, std::vector<int64_t>& idx, std::vector<double>& score) const
+            {
+                const int64_t M = points.size();
+                if (q < 0 || q > GPE_SELECT_MAX_ROUNDS || rule < GPE_SELECT_UCB || rule > GPE_SELECT_VAR || !std::isfinite(param)
+                    || (rule == GPE_SELECT_UCB && param < 0) || !(var_add >= 0) || !std::isfinite(var_add) || !(obs_noise >= 0)
+                    || !std::isfinite(obs_noise) || (distinct && q > M && M > 0) || (!mu.empty() && (int64_t)mu.size() != M))
+                    throw std::invalid_argument("limbo_amd: select_batch(): bad argument (include/gpe_batch_select.h)");
+                idx.assign((size_t)q, -1);
+                score.assign((size_t)q, 0.0);
+                if (M == 0 || q == 0) {
+                    idx.clear();
+                    score.clear();
+                    return 0;
+                }
+                int rc = 0;
+                if (_joint_on_host(M)) {
+                    std::vector<double> kta((size_t)(M * _dim_out)), cov((size_t)(M * M)), var((size_t)M), W((size_t)(M * q));
+                    _host_joint(points, kta.data(), cov.data(), 0.0);
+                    rc = limbo_amd::host_small::select_greedy(cov.data(), M, M, mu.empty() ? kta.data() : mu.data(), q, rule, param, var_add,
+                        obs_noise, distinct, idx.data(), score.data(), var.data(), W.data());
+                }
+                else {
+                    const std::vector<double> Xq = _joint_points(points);
+                    rc = _eng.check(gpe_select_batch(_eng.get(), Xq.data(), M, q, rule, param, mu.empty() ? nullptr : mu.data(), var_add, obs_noise,
+                                        distinct ? 1 : 0, idx.data(), score.data(), nullptr, nullptr, 0),
+                        "gpe_select_batch");
+                }
+                if (rc > 0) {
+                    idx.resize((size_t)rc);
+                    score.resize((size_t)rc);
+                }
+                return rc;
             }
 
             /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise

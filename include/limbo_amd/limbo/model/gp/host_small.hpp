@@ -149,6 +149,70 @@ namespace limbo_amd {
             row[n] = std::sqrt(d);
             return d > 0.0 ? 0 : (int)(n + 1);
         }
+        /// The score of one candidate in greedy batch selection (include/gpe_batch_select.h): rule 0 UCB (param = beta), 1 EI
+        /// (param = f+ + jitter; acqui/ei.hpp: _value), 2 the variance; var_add enters behind the clamp of gp.hpp:623
+        inline double select_score(int rule, double mu, double var, double var_add, double param)
+        {
+            const double s2 = (var <= 2.220446049250313e-16 ? 0.0 : var) + var_add;
+            if (rule == 2)
+                return s2;
+            const double sigma = std::sqrt(s2);
+            if (rule == 0)
+                return mu + param * sigma;
+            if (sigma < 1e-10)
+                return 0.0;
+            const double X = mu - param, Z = X / sigma;
+            const double phi = std::exp(-0.5 * Z * Z) / std::sqrt(2.0 * M_PI);
+            const double Phi = 0.5 * std::erfc(-Z / std::sqrt(2));
+            return X * Phi + sigma * phi;
+        }
+        /// The recursion of include/gpe_batch_select.h on a full posterior covariance Sig (M x M, column-major, lds; no jitter
+        /// on its diagonal): q greedy picks, each followed by a rank-1 downdate of the variance by a hallucinated observation
+        /// of noise obs_noise.  W: M x q scratch (ld M) that holds the columns afterwards; var: M, out (var_q, no clamp);
+        /// idx, score: q.  Returns 0, or t + 1 for the first round t whose pivot is not positive (idx / score of rounds <= t
+        /// are set).
+        inline int select_greedy(const double* Sig, int64_t M, int64_t lds, const double* mu, int q, int rule, double param, double var_add,
+            double obs_noise, bool distinct, int64_t* idx, double* score, double* var, double* W)
+        {
+            for (int64_t m = 0; m < M; ++m)
+                var[m] = Sig[m + m * lds];
+            for (int t = 0; t < q; ++t) {
+                int64_t j = -1;
+                double best = 0.0;
+                for (int64_t m = 0; m < M; ++m) {
+                    bool taken = false;
+                    for (int s = 0; distinct && s < t && !taken; ++s)
+                        taken = idx[s] == m;
+                    if (taken)
+                        continue;
+                    const double v = select_score(rule, mu[m], var[m], var_add, param);
+                    if (v == v && (j < 0 || v > best)) { // (ascending m: `>` keeps the lowest index of equal values)
+                        best = v;
+                        j = m;
+                    }
+                }
+                idx[t] = j;
+                score[t] = j < 0 ? std::nan("") : best;
+                if (j < 0)
+                    return t + 1;
+                double* w = W + (int64_t)t * M;
+                for (int64_t m = 0; m < M; ++m) {
+                    double c = Sig[m + j * lds];
+                    for (int s = 0; s < t; ++s)
+                        c -= W[m + (int64_t)s * M] * W[j + (int64_t)s * M];
+                    w[m] = c;
+                }
+                const double piv = w[j] + obs_noise;
+                if (!(piv > 0.0) || !std::isfinite(piv))
+                    return t + 1;
+                const double r = std::sqrt(piv);
+                for (int64_t m = 0; m < M; ++m) {
+                    w[m] /= r;
+                    var[m] -= w[m] * w[m];
+                }
+            }
+            return 0;
+        }
     } // namespace host_small
 } // namespace limbo_amd
 #endif

@@ -20,6 +20,7 @@ ENGINE_SO = _PKG / "libgpengine.so"
 
 KERNEL_SE_ARD, KERNEL_MATERN52, KERNEL_MATERN32, KERNEL_EXP, KERNEL_HOST_K = range(5)
 KERNEL_NAMES = {"se_ard": 0, "matern52": 1, "matern32": 2, "exp": 3, "host_k": 4}
+SELECT_UCB, SELECT_EI, SELECT_VAR = range(3)  # include/gpe_batch_select.h: the rules of select_batch
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -142,6 +143,11 @@ def _sig(lib, prefix):
             "paths_info": [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
             "paths_phase_ms": [_vp, _dp],
             "paths_destroy": [_vp],
+            # include/gpe_batch_select.h: greedy batch selection with hallucinated observations
+            "select_batch": [_vp, _dp, _i64, C.c_int, C.c_int, C.c_double, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(_i64), _dp, _dp,
+                             _dp, _i64],
+            "select_phase_ms": [_vp, _dp],
+            "debug_select_plan": [_i64, _i64, C.c_int, C.POINTER(_i64), _i64],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -428,6 +434,34 @@ class Handle:
         self._chk(self.lib.fn("joint_max_points")(self._h, C.byref(n)), "joint_max_points")
         return n.value
 
+    # -- greedy batch selection with hallucinated observations (include/gpe_batch_select.h; HIP library only)
+    def select_batch(self, Xq, q, rule, param, mu_q=None, var_add=0.0, obs_noise=0.0, distinct=True, want=("idx", "score", "var", "W"),
+                     check=True):
+        """q greedy picks among the rows of Xq.  rule: SELECT_UCB (param = beta), SELECT_EI (param = f+ + jitter) or SELECT_VAR.
+        Returns (status, idx (q), score (q), var (M), W (M, q)), None for what `want` leaves out; status > 0 is the 1-based round
+        whose pivot was not positive (rounds before it are valid).  check=False hands a negative GPE_ERR_* back instead of raising."""
+        Xq = _c(Xq).reshape(-1, self.D)
+        M, q = Xq.shape[0], int(q)
+        mq = _c(np.asarray(mu_q, dtype=np.float64).reshape(M)) if mu_q is not None else None
+        idx = np.zeros(max(q, 0), dtype=np.int64) if "idx" in want else None
+        score = np.zeros(max(q, 0)) if "score" in want else None
+        var = np.zeros(M) if "var" in want else None
+        W = np.zeros((M, max(q, 0)), order="F") if "W" in want else None
+        rc = self.lib.fn("select_batch")(self._h, _d(Xq), M, q, int(rule), float(param), _d(mq) if mq is not None else None, float(var_add),
+                                         float(obs_noise), int(bool(distinct)),
+                                         idx.ctypes.data_as(C.POINTER(_i64)) if idx is not None else None,
+                                         _d(score) if score is not None else None, _d(var) if var is not None else None,
+                                         _d(W) if W is not None else None, max(M, 1))
+        if check:
+            self._chk(rc, "select_batch")
+        return rc, idx, score, var, W
+
+    def select_phase_ms(self):
+        """{setup, rounds, readback} of the last select_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("select_phase_ms")(self._h, _d(ms)), "select_phase_ms")
+        return dict(zip(("setup", "rounds", "readback"), ms.tolist()))
+
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)
     def query_batch_grad(self, Xq, want=("kta", "var", "dkta", "dvar")):
         """(kta (M, P), var (M), dkta (M, D, P), dvar (M, D)), None for what `want` leaves out: dkta[m, d, p] = d(k^T alpha_p)/dv_d,
@@ -676,6 +710,16 @@ def debug_cov_plan(lib, M, N, cus):
         raise EngineError(f"debug_cov_plan: bad arguments ({M}, {N}, {cus})")
     out = np.zeros((n, 5), dtype=np.int64)
     lib.fn("debug_cov_plan")(int(M), int(N), int(cus), out.ctypes.data_as(C.POINTER(_i64)), n)
+    return out
+
+
+def debug_select_plan(lib, M, N, cus):
+    """gpe_debug_select_plan: the (m0, m1, k0, k1, partial slot) rows of one round's column product, as an int64 array."""
+    n = lib.fn("debug_select_plan")(int(M), int(N), int(cus), None, 0)
+    if n < 0:
+        raise EngineError(f"debug_select_plan: bad arguments ({M}, {N}, {cus})")
+    out = np.zeros((n, 5), dtype=np.int64)
+    lib.fn("debug_select_plan")(int(M), int(N), int(cus), out.ctypes.data_as(C.POINTER(_i64)), n)
     return out
 
 

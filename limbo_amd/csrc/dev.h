@@ -496,6 +496,48 @@ void launch_draws(hipStream_t s, const double* Cm, int64_t ldc, int64_t M, const
 // out[2 col] = max of column col of F, out[2 col + 1] = the bits of the lowest index (int64) that holds it
 void launch_argmax(hipStream_t s, const double* F, int64_t M, int ncols, double* out);
 
+// ---- greedy batch selection with hallucinated observations (select.hip; include/gpe_batch_select.h) --------------------
+#define SEL_RULE_UCB 0
+#define SEL_RULE_EI 1
+#define SEL_RULE_VAR 2
+// the words the rounds hand on from launch to launch (device memory, zeroed before the first launch)
+struct SelState {
+    long long j;    // this round's pick
+    long long fail; // 0, or the status of the call: the 1-based round whose pivot was not positive; every later launch returns at once
+    long long bad;  // set by k_sel_fold of a round with such a pivot, turned into `fail` by the launch behind it
+};
+int select_chunks(int64_t M, int64_t N, int cus);
+int select_fold_groups(int64_t M); // workgroups of the fold = (value, index) pairs a round leaves
+int select_plan(int64_t M, int64_t N, int cus, int64_t* out, int64_t cap_rows); // host only: gpe_debug_select_plan
+struct SelRound {
+    SelState* st;
+    const int64_t* plan; // device copy of select_plan's rows
+    int64_t nrows;
+    int nch;
+    const double* Zt; // Zt[m + i ldz], i < N
+    int64_t ldz, N, M;
+    const double* Qt; // the candidates, SoA
+    int64_t ldq;
+    const KParams* kp; // host copy
+    double *zj, *wj;   // row j of Zt (N) and of W (q)
+    double* part;      // nch partial vectors, ldp apart
+    int64_t ldp;
+    double* W; // M x q
+    int64_t ldw;
+    double* var;      // var_t, updated in place
+    const double* mu; // M
+    int* picked;      // M, zeroed
+    double* pairs;    // 2 per workgroup of the fold
+    long long* idx;   // q
+    double* score;    // q
+    int q, rule, distinct;
+    double param, var_add, obs_noise;
+};
+// Zt[m + i ldz] = Z[i + m ld] (the N x M layout of the small models, once per call)
+void launch_sel_transpose(hipStream_t s, const double* Z, int64_t ld, int64_t N, int64_t M, double* Zt, int64_t ldz);
+void launch_sel_score0(hipStream_t s, const SelRound& g);      // the scores of round 0 and its pick
+void launch_sel_round(hipStream_t s, const SelRound& g, int t); // round t: gather, column product, fold, the pick of round t + 1
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);
