@@ -222,7 +222,7 @@ int gpe_small_calls(gpe_handle h, int64_t* n);
 int gpe_trace(int on);
 int gpe_trace_dump(const char* path);
 /* Test hook, host only (no device is touched): the dispatch table of a data-flow launch of `nt` tile columns x `nb` row strips
- * (csrc/potrf_tail.hip: tail_order; lag = GPE_TAIL_LAG; pair: must be 0, the form it selected left in round 6) is built and checked — 1: a permutation of the launch's
+ * (csrc/potrf_tail.hip: tail_order; lag: the launches use 3; pair: must be 0, the form it selected left in round 6) is built and checked — 1: a permutation of the launch's
  * tiles in which every workgroup waits for lower-numbered ones only (what makes the launch deadlock-free), 0: not, -1: bad
  * arguments.  The engine runs the same check before it uses a table. */
 int gpe_debug_tail_order(int nt, int nb, int lag, int pair);

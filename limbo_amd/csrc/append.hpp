@@ -105,7 +105,7 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
     }
     // Point by point — gpe_add_sample's launches AND its host wait per point (one launch and a spin on a pinned word on the small
     // path, the three sweeps and a stream wait above it) — while the model has less than one outer panel (the transposed solve
-    // needs one), when the whole append stays inside the one-launch small path, and for a panel width that layout does not serve
+    // needs one) and when the whole append stays inside the one-launch small path
     const bool small_all = c->small_path && nfin <= small_max_n() && P <= 3;
     int status = 0;
     int64_t done = 0;

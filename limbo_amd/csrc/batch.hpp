@@ -7,7 +7,7 @@
 static bool batch_compatible(const gpe_ctx* a, const gpe_ctx* b)
 {
     return a->device == b->device && a->N == b->N && a->D == b->D && a->P == b->P && a->cap == b->cap && a->ld == b->ld
-        && a->nbo == b->nbo && a->fuse_panel == b->fuse_panel && a->flow_solve == b->flow_solve && !a->host_K && !b->host_K
+        && a->fuse_panel == b->fuse_panel && a->flow_solve == b->flow_solve && !a->host_K && !b->host_K
         && a->kind != GPE_KERNEL_HOST_K && b->kind != GPE_KERNEL_HOST_K && a->n_theta == b->n_theta
         && ((a->kind == GPE_KERNEL_SE_ARD) == (b->kind == GPE_KERNEL_SE_ARD)) && a->dA && b->dA && !a->prof && !b->prof;
 }
@@ -199,8 +199,7 @@ static int batch_compute_impl(gpe_handle* hs, int G, int* status, const BatchWan
     for (int g = 0; g < G && fused; ++g) {
         gpe_ctx* c = hs[g];
         fused = c && c->N > 0 && batch_compatible(hs[0], c) && lam_columns(c->kind, c->n_theta, c->D) == 0
-            && c->flow_solve && (c->N + NB - 1) / NB <= 256
-            && (!(want && want->grad) || (c->nbo % 128 == 0 && c->nbo <= 256)); // (K^-1: the one-launch panel inverses)
+            && c->flow_solve && (c->N + NB - 1) / NB <= 256;
         for (int q = 0; q < g && fused; ++q)
             fused = hs[q] != c; // the same handle twice cannot be stepped in parallel
     }
@@ -216,24 +215,21 @@ static int batch_compute_impl(gpe_handle* hs, int G, int* status, const BatchWan
             DevGuard dg(c);
         }
         int worst = GPE_OK;
-        // Sub-batches of <= GPE_BT_MAXG GPs, up to four in flight on their own streams: while one sub-batch is in its
-        // panel steps (latency-bound workgroups, one per CU) another one's matrix-core updates fill the chip.
-        static const int nsub_env = (int)env_int("GPE_BATCH_SPLIT", 2);
-        int nsub = std::max(1, std::min(4, nsub_env));
-        if (G < 16)
-            nsub = 1;
+        // Sub-batches of <= GPE_BT_MAXG GPs, two in flight on their own streams from 16 members on: while one sub-batch is in
+        // its panel steps (latency-bound workgroups, one per CU) the other one's matrix-core updates fill the chip.
+        const int nsub = G < 16 ? 1 : 2;
         const int per = std::min(GPE_BT_MAXG, (G + nsub - 1) / nsub);
         for (int g0 = 0; g0 < G;) {
             // one wave of sub-batches
-            int starts[4], counts[4], nw = 0;
+            int starts[2], counts[2], nw = 0;
             for (; nw < nsub && g0 < G; ++nw) {
                 starts[nw] = g0;
                 counts[nw] = std::min(per, G - g0);
                 g0 += counts[nw];
             }
-            int en[4];
-            BatchTab* tabs[4] = {nullptr, nullptr, nullptr, nullptr};
-            BatchWant wsub[4];
+            int en[2];
+            BatchTab* tabs[2] = {nullptr, nullptr};
+            BatchWant wsub[2];
             for (int w = 0; w < nw; ++w) {
                 if (want) {
                     wsub[w] = *want;

@@ -90,6 +90,7 @@ void gpe_trace_add(const char* name, hipStream_t s, hipEvent_t e0, hipEvent_t e1
 }
 
 #define NB 64
+#define NBO 256 // outer panel width of the two-level blocked algorithms: four blocks of NB
 // pinned staging of the small path: results in [0, 256), inputs (obs_mean: (n + 1) x P <= 257 x 3; query points: 8 x 64) from 256 on
 #define SMALL_STAGE_DOUBLES (256 + 1024)
 
@@ -132,13 +133,9 @@ struct gpe_ctx {
     int64_t tail_cap = 0, tall_cap = 0; // doubles per buffer of the closing / tall pair
     unsigned tail_count = 0, tall_count = 0;
     int64_t tail_lay = -1, tall_lay = -1; // nt * 65536 + nb of the pair's previous launch (-1: both buffers entirely all-ones)
-    int gen_mode = 0; // this evaluation's data-flow launches generate their own tiles of K (compute_enqueue): 0 no, 1 the one
-                      // launch that is the whole factorisation, 2 the tall launch (the rest of K is built beside it)
-    hipEvent_t gen_ev = nullptr;
+    bool gen_mode = false; // this evaluation: the one launch that is the whole factorisation generates K (compute_enqueue)
     unsigned p256_count = 0;           // launches of k_panel256 so far: its polled X22 copies alternate between two buffers
     std::vector<hipEvent_t> pl_events; // ... one per outer panel: the one-launch panel is complete (early release of the look-ahead stream)
-    int64_t early_bulk = 100;          // release the look-ahead stream at the END OF THE PANEL (not of the fused next-panel update)
-                                       // when the far update has at least this many 128 x 128 tiles (GPE_EARLY_BULK_TILES; -1: never)
     bool stop_events = true;    // next-panel update signals through its own dispatch (hipExtLaunchKernel stop event)
     bool fuse_diag = true;      // next diagonal block factored inside the next-panel update launch (k_upd_fused)
     bool lookahead = true;             // GPE_LOOKAHEAD=0 disables
@@ -163,7 +160,7 @@ struct gpe_ctx {
     int64_t handover_reruns = 0;    // evaluations re-run after a hand-over timeout (gpe_handover_reruns)
     DevBuf<double> dXinv; // transposed inverses of the 64 x 64 diagonal blocks of L, 4096 doubles each
     bool panel256 = true;    // all steps of a 256-column outer panel in one data-flow launch (GPE_PANEL256=0: step by step)
-    DevBuf<double> dXp;      // inverses of the nbo x nbo diagonal panels of L, compact (ensure_inv with the overlapped product)
+    DevBuf<double> dXp;      // inverses of the NBO x NBO diagonal panels of L, compact (ensure_inv with the overlapped product)
     DevBuf<double> dInvS;    // the recursive K^-1's scratch (inv2.hip): T-forms / W | three partial buffers, ld x cap each
     int invS_bufs = 0;       // ... how many ld x cap buffers it holds: 1 + inv2_partials() for a single handle, 1 for a member of a
                              // batch of >= 4 (whose plan cuts no k range: ADVICE r5 — 64 x N = 4096 used to reserve 26 GB it never touched)
@@ -182,7 +179,6 @@ struct gpe_ctx {
     int* hInfo = nullptr;    // view: hPinned + 0
     double* hScal = nullptr; // view: hPinned + 128
     bool have_L = false, inv_ok = false, host_K = false, ll_ok = false;
-    int nbo = 256; // outer panel width of the two-level blocked algorithms
     // one-launch small-N path (small.hip): pinned staging the kernels read / write directly, the word the host spins on
     char* hPinned = nullptr;             // the HandleShell's pinned allocation behind hInfo / hSmallSeq / hScal / hSmall
     double* hSmall = nullptr;            // view: hScal + 1024.  [0..2): log-lik terms | [16 .. 16+8*GPE_MAX_P+8): kta, var | [256..): obs_mean / query points in
@@ -675,7 +671,6 @@ int gpe_create(int device_id, gpe_handle* out)
     c->panel_handover_cfg = c->panel_handover;
     c->fuse_diag = env_flag("GPE_FUSE_DIAG", c->fuse_diag);
     c->panel256 = env_flag("GPE_PANEL256", c->panel256);
-    c->early_bulk = env_int("GPE_EARLY_BULK_TILES", c->early_bulk);
     if (const char* f = getenv("GPE_TAIL_MAX")) {
         c->tail_max = std::min<int64_t>(std::max<int64_t>(atoll(f), 0), GPE_TAIL_MAX);
         c->tail_single = 0;
@@ -689,12 +684,6 @@ int gpe_create(int device_id, gpe_handle* out)
     c->lookahead = env_flag("GPE_LOOKAHEAD", c->lookahead);
     c->flow_solve = env_flag("GPE_FLOW_SOLVE", c->flow_solve);
     c->fuse_panel = env_flag("GPE_FUSE_PANEL", c->fuse_panel);
-    const char* e = getenv("GPE_NBO");
-    if (e) {
-        int v = atoi(e);
-        if (v >= 64 && v % 64 == 0)
-            c->nbo = v;
-    }
     *out = c;
     return GPE_OK;
 }
@@ -709,8 +698,6 @@ int gpe_destroy(gpe_handle c)
         gpe_destroy(c->joint);
         c->joint = nullptr;
     }
-    if (c->gen_ev)
-        hipEventDestroy(c->gen_ev);
     if (c->inv_ev) {
         hipEventDestroy(c->inv_ev);
         hipEventDestroy(c->inv_ev0);
@@ -1177,8 +1164,7 @@ int gpe_hp_objective(gpe_handle c, int kind, const double* th, int n_theta, doub
     int rc = gpe_set_kernel(c, kind, th, n_theta, noise); // kernel_lf_opt.hpp:80
     if (rc)
         return rc;
-    static const bool fused_ok = env_not_zero("GPE_HP_FUSED");
-    if (want_grad && grad && fused_ok) {
+    if (want_grad && grad) {
         // Round 5: ONE enqueue for the whole objective — factorisation, alpha, log-lik terms, K^-1, gradient — and one wait.
         // The separate calls below cost a host round trip between the sweep and K^-1 (~20 us of idle chip), and K^-1's
         // lowest level (latency-bound launches on an eighth of the chip) can now run on the second stream BESIDE the sweep
@@ -1527,7 +1513,6 @@ int gpe_clone_to(gpe_handle src, int device_id, gpe_handle* out)
     c->n_theta = src->n_theta;
     memcpy(c->theta, src->theta, sizeof(c->theta));
     c->noise = src->noise;
-    c->nbo = src->nbo;
     c->fuse_panel = src->fuse_panel;
     c->flow_solve = src->flow_solve;
     c->small_path = src->small_path;

@@ -684,12 +684,11 @@ static void launch_glds128(hipStream_t s, const GemmArgs& g0)
     const int tiles_m = (int)((g.m + TM - 1) / TM), tiles_n = (int)((g.n + TN - 1) / TN);
     int64_t tiles = (int64_t)tiles_m * tiles_n;
     g.tile_map = nullptr;
-    static const bool tri_map = env_not_zero("GPE_TRI_MAP");
     int mapped = 0;
     // (not for batched launches: measured slower there — 8 x 2048 6.44 against 6.70 k evaluations/s, 64 x 2048 8.53 against 8.80:
     // the members' small updates are dealt over the chip by gridDim.z, a member's few tiles gain nothing from the order and lose
     // the padding to whole rounds of eight)
-    if (g.tri && tri_map && !g_batch.bt && tiles_m < 65536 && tiles_n < 32768)
+    if (g.tri && !g_batch.bt && tiles_m < 65536 && tiles_n < 32768)
         g.tile_map = tri_tile_map(g, &mapped);
     if (g.tile_map)
         tiles = mapped;
@@ -1014,14 +1013,13 @@ static int64_t live_tiles(const GemmArgs& g, int TM, int TN)
     return cnt;
 }
 
-static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g, int use_glds64, int force);
+static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g);
 void launch_gemm_sub(hipStream_t s, const GemmArgs& g0)
 {
     if (g0.m <= 0 || g0.n <= 0)
         return;
     if (g0.k <= 0 && !g0.overwrite)
         return;
-    const int use_glds64 = 1, force = 0; // (the tile is picked by problem size below; GemmArgs::tile forces one)
     if (g0.rhs_rows > 0) {
         // Right-hand-side rows as FMAs inside the kernel (gemm_glds64.h) instead of a row of tiles: the FMAs cost every
         // workgroup ~4 us before its first tile, the tile row costs n / 128 extra workgroups — which only matters when
@@ -1031,29 +1029,29 @@ void launch_gemm_sub(hipStream_t s, const GemmArgs& g0)
         GemmArgs q = g0;
         q.m = g0.m - g0.rhs_rows;
         q.rhs_rows = 0; // (for the tile counts below)
-        static const int rhs_fma = (int)env_int("GPE_RHS_FMA", 1); // 0: never, 2: always
         bool fma = false;
-        if (rhs_fma && q.m > 0 && !q.overwrite && glds_ok(q) && g_batch.G == 1) {
+        if (q.m > 0 && !q.overwrite && glds_ok(q) && g_batch.G == 1) {
             auto crosses = [&](int T, int64_t round) { return live_tiles(q, T, T) <= round && live_tiles(g0, T, T) > round; };
-            fma = rhs_fma == 2 || crosses(128, 256) || (live_tiles(g0, 128, 128) < 200 && (crosses(64, 512) || crosses(64, 256)));
+            fma = crosses(128, 256) || (live_tiles(g0, 128, 128) < 200 && (crosses(64, 512) || crosses(64, 256)));
         }
         if (fma) {
             q.rhs_rows = g0.rhs_rows;
-            launch_gemm_sub_impl(s, q, use_glds64, force);
+            launch_gemm_sub_impl(s, q);
         }
         else {
             q = g0;
             q.rhs_rows = 0;
-            launch_gemm_sub_impl(s, q, use_glds64, force);
+            launch_gemm_sub_impl(s, q);
         }
         return;
     }
-    launch_gemm_sub_impl(s, g0, use_glds64, force);
+    launch_gemm_sub_impl(s, g0);
 }
 
-static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g, int use_glds64, int force)
+// (the tile is picked by problem size; GemmArgs::tile forces one)
+static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g)
 {
-    int tile = g.tile ? g.tile : force;
+    int tile = g.tile;
     if (tile != 128 && tile != 64 && tile != 32) {
         // measured at k = 256 (tools/kbench): one 128 x 128 glds workgroup per CU runs at the
         // LDS-fed MFMA rate (~48 us per tile); below ~200 live tiles too many CUs idle and the
@@ -1062,7 +1060,7 @@ static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g, int use_glds6
         const int64_t t128_min = 200;
         if (glds_ok(g) && GB * live_tiles(g, 128, 128) >= t128_min)
             tile = 128;
-        else if (glds_ok(g) && !g.ktri && use_glds64 && GB * live_tiles(g, 64, 64) >= 96) // (the 64 x 64 body has no ktri form)
+        else if (glds_ok(g) && !g.ktri && GB * live_tiles(g, 64, 64) >= 96) // (the 64 x 64 body has no ktri form)
             tile = 64; // deep-prefetch 64 x 64 glds kernel: also the latency-critical next-panel update
         else if (GB * live_tiles(g, 64, 64) >= 512)
             tile = 64;
@@ -1071,12 +1069,12 @@ static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g, int use_glds6
     }
     if (g.rhs_rows > 0) {
         // right-hand-side rows are FMAs inside the direct-to-LDS kernels only; any other kernel takes them as ordinary rows
-        const bool direct = glds_ok(g) && (tile == 128 || (tile == 64 && !g.ktri && use_glds64));
+        const bool direct = glds_ok(g) && (tile == 128 || (tile == 64 && !g.ktri));
         if (!direct) {
             GemmArgs q = g;
             q.m += q.rhs_rows;
             q.rhs_rows = 0;
-            launch_gemm_sub_impl(s, q, use_glds64, force);
+            launch_gemm_sub_impl(s, q);
             return;
         }
     }
@@ -1086,7 +1084,7 @@ static void launch_gemm_sub_impl(hipStream_t s, const GemmArgs& g, int use_glds6
         launch_glds128(s, g);
     else if (tile == 128)
         launch_tile<128, 128, 32, 2>(s, g);
-    else if (tile == 64 && glds_ok(g) && !g.ktri && use_glds64)
+    else if (tile == 64 && glds_ok(g) && !g.ktri)
         launch_glds64(s, g);
     else if (tile == 64)
         launch_tile<64, 64, 32, 2>(s, g);

@@ -94,144 +94,117 @@ int ensure_inv(gpe_ctx* c)
         c->inv_ok = true; // gp.hpp:263
         return GPE_OK;
     }
-    static const bool inv_panels = env_not_zero("GPE_INV_PANELS");
-    c->inv_pad_n = -1; // (the forms below write whole tiles of the U buffer)
-    if (inv_panels && c->nbo % 128 == 0 && c->nbo <= 256) {
-        // Transposed formulation: U = L^-T (upper triangular) is built in dLinv, K^-1 = U U^T.  Every product below
-        // is C (-/+)= A B^T with A and B contiguous along their non-k index — the operand layout of the LDS-direct
-        // matrix-core kernel (gemm.hip) — and k = the panel width, the shape of the Cholesky trailing update.
-        //   inv.hip        : X_p = inv(L_pp) for every outer panel p in one launch -> diagonal blocks of T (= the
-        //                    K^-1 buffer, free until the last step), X_p^T -> diagonal blocks of U
-        //   U[0:o0, p]     = AccT[0:o0, p] X_p^T                       (AccT = -sum_{q<p} U[:, q] L[p, q]^T, in T)
-        //   AccT[0:oe, p+1..] -= U[0:oe, p] L[p+1.., p]^T
-        //   K^-1 = U U^T                                              (one launch)
-        const int64_t nbo = c->nbo;
-        const int64_t npan = (N + nbo - 1) / nbo;
-        // Round 3: K^-1 = sum_p U[:, p] U[:, p]^T is accumulated panel by panel on the SECOND stream while the main stream
-        // is still building the later panels of U — that chain is a string of small dependent launches that leaves most
-        // of the chip idle, and panel p's rank-k update only needs U's panel p.  (As a replacement for the one-launch
-        // product the 16 accumulating launches were slower, 761 against 704 us: they re-read C; underneath the chain they
-        // are free.)  The X_p now live in a compact side buffer, so the K^-1 buffer's diagonal blocks are free from the start.
-        // Batched launches, profiling runs and GPE_INV_OVERLAP=0 keep everything on one stream, product last, as before.
-        static const bool overlap_ok = env_not_zero("GPE_INV_OVERLAP");
-        const bool overlap = overlap_ok && !g_batch.bt && !c->prof && c->stop_events && npan >= 4;
-        if (overlap)
-            HIPCHK(c, c->dXp.reserve((size_t)(npan * nbo * nbo)));
-        auto ev = [&](size_t i) {
-            while (c->la_events.size() <= i) {
-                hipEvent_t e;
-                hipEventCreateWithFlags(&e, hipEventDisableTiming);
-                c->la_events.push_back(e);
-            }
-            return c->la_events[i];
-        };
-        {
-            PhaseScope ps(c, GPE_PH_INV, 0.0);
-            // (a kernel: it takes part in batched launches, dev.h).  With the overlap only the second stream's rank-k updates
-            // touch the K^-1 buffer: it is zeroed there, beside the block inverses instead of in front of them (21 us + a
-            // launch boundary of every gradient evaluation); that stream's work of the factorisation was joined long ago, and
-            // whatever read the buffer last on the main stream precedes the events those launches waited for
-            launch_zero2d(overlap ? c->stream2 : s, c->dKinv, ld, N, N);
-            if (overlap)
-                launch_inv_panels(s, c->dA, ld, N, (int)nbo, c->dXinv, c->dXp, 0, c->dLinv, ld); // X_p compact, X_p^T -> U's diagonal blocks
-            else
-                launch_inv_panels(s, c->dA, ld, N, (int)nbo, c->dXinv, c->dKinv, ld, c->dLinv, ld);
+    c->inv_pad_n = -1; // (the panel form below writes whole tiles of the U buffer)
+    // Transposed formulation: U = L^-T (upper triangular) is built in dLinv, K^-1 = U U^T.  Every product below
+    // is C (-/+)= A B^T with A and B contiguous along their non-k index — the operand layout of the LDS-direct
+    // matrix-core kernel (gemm.hip) — and k = the panel width, the shape of the Cholesky trailing update.
+    //   inv.hip        : X_p = inv(L_pp) for every outer panel p in one launch -> diagonal blocks of T (= the
+    //                    K^-1 buffer, free until the last step), X_p^T -> diagonal blocks of U
+    //   U[0:o0, p]     = AccT[0:o0, p] X_p^T                       (AccT = -sum_{q<p} U[:, q] L[p, q]^T, in T)
+    //   AccT[0:oe, p+1..] -= U[0:oe, p] L[p+1.., p]^T
+    //   K^-1 = U U^T                                              (one launch)
+    const int64_t nbo = NBO;
+    const int64_t npan = (N + nbo - 1) / nbo;
+    // Round 3: K^-1 = sum_p U[:, p] U[:, p]^T is accumulated panel by panel on the SECOND stream while the main stream
+    // is still building the later panels of U — that chain is a string of small dependent launches that leaves most
+    // of the chip idle, and panel p's rank-k update only needs U's panel p.  (As a replacement for the one-launch
+    // product the 16 accumulating launches were slower, 761 against 704 us: they re-read C; underneath the chain they
+    // are free.)  The X_p now live in a compact side buffer, so the K^-1 buffer's diagonal blocks are free from the start.
+    // Batched launches, profiling runs and fewer than four panels keep everything on one stream, product last, as before.
+    const bool overlap = !g_batch.bt && !c->prof && c->stop_events && npan >= 4;
+    if (overlap)
+        HIPCHK(c, c->dXp.reserve((size_t)(npan * nbo * nbo)));
+    auto ev = [&](size_t i) {
+        while (c->la_events.size() <= i) {
+            hipEvent_t e;
+            hipEventCreateWithFlags(&e, hipEventDisableTiming);
+            c->la_events.push_back(e);
         }
-        auto rank_update = [&](hipStream_t st, int64_t o0, int64_t pw) { // K^-1[0:oe, 0:oe] += U[0:oe, p] U[0:oe, p]^T, lower triangle
+        return c->la_events[i];
+    };
+    {
+        PhaseScope ps(c, GPE_PH_INV, 0.0);
+        // (a kernel: it takes part in batched launches, dev.h).  With the overlap only the second stream's rank-k updates
+        // touch the K^-1 buffer: it is zeroed there, beside the block inverses instead of in front of them (21 us + a
+        // launch boundary of every gradient evaluation); that stream's work of the factorisation was joined long ago, and
+        // whatever read the buffer last on the main stream precedes the events those launches waited for
+        launch_zero2d(overlap ? c->stream2 : s, c->dKinv, ld, N, N);
+        if (overlap)
+            launch_inv_panels(s, c->dA, ld, N, (int)nbo, c->dXinv, c->dXp, 0, c->dLinv, ld); // X_p compact, X_p^T -> U's diagonal blocks
+        else
+            launch_inv_panels(s, c->dA, ld, N, (int)nbo, c->dXinv, c->dKinv, ld, c->dLinv, ld);
+    }
+    auto rank_update = [&](hipStream_t st, int64_t o0, int64_t pw) { // K^-1[0:oe, 0:oe] += U[0:oe, p] U[0:oe, p]^T, lower triangle
+        GemmArgs g{};
+        g.C = c->dKinv;
+        g.ldc = ld;
+        g.A = c->dLinv + o0 * ld;
+        g.lda = ld;
+        g.B = c->dLinv + o0 * ld;
+        g.ldb = ld;
+        g.m = g.n = o0 + pw;
+        g.k = pw;
+        g.tri = 1;
+        g.overwrite = 2;
+        launch_gemm_sub(st, g);
+    };
+    if (overlap) {
+        hipEventRecord(ev(0), s); // zeroed K^-1 buffer, block inverses: panel 0 of U is complete
+        hipStreamWaitEvent(c->stream2, ev(0), 0);
+        rank_update(c->stream2, 0, std::min<int64_t>(nbo, N));
+    }
+    for (int64_t o0 = 0; o0 < N; o0 += nbo) {
+        const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
+        if (o0 > 0) {
             GemmArgs g{};
-            g.C = c->dKinv;
+            g.C = c->dLinv + o0 * ld;
+            g.ldc = ld;
+            g.A = c->dKinv + o0 * ld;
+            g.lda = ld;
+            g.B = overlap ? c->dXp + (o0 / nbo) * (nbo * nbo) : c->dKinv + o0 + o0 * ld;
+            g.ldb = overlap ? nbo : ld;
+            g.m = o0;
+            g.n = pw;
+            g.k = pw;
+            g.overwrite = 1;
+            if (overlap)
+                g.stop_event = ev((size_t)(o0 / nbo)); // this launch's own completion: panel p of U is final
+            PhaseScope ps(c, GPE_PH_INV, gemm_flops(g));
+            launch_gemm_sub(s, g);
+            if (overlap) {
+                hipStreamWaitEvent(c->stream2, ev((size_t)(o0 / nbo)), 0);
+                rank_update(c->stream2, o0, pw);
+            }
+        }
+        if (oe < N) {
+            GemmArgs g{};
+            g.C = c->dKinv + oe * ld;
             g.ldc = ld;
             g.A = c->dLinv + o0 * ld;
             g.lda = ld;
-            g.B = c->dLinv + o0 * ld;
+            g.B = c->dA + oe + o0 * ld;
             g.ldb = ld;
-            g.m = g.n = o0 + pw;
+            g.m = oe;
+            g.n = N - oe;
             g.k = pw;
-            g.tri = 1;
-            g.overwrite = 2;
-            launch_gemm_sub(st, g);
-        };
-        if (overlap) {
-            hipEventRecord(ev(0), s); // zeroed K^-1 buffer, block inverses: panel 0 of U is complete
-            hipStreamWaitEvent(c->stream2, ev(0), 0);
-            rank_update(c->stream2, 0, std::min<int64_t>(nbo, N));
-        }
-        for (int64_t o0 = 0; o0 < N; o0 += nbo) {
-            const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
-            if (o0 > 0) {
-                GemmArgs g{};
-                g.C = c->dLinv + o0 * ld;
-                g.ldc = ld;
-                g.A = c->dKinv + o0 * ld;
-                g.lda = ld;
-                g.B = overlap ? c->dXp + (o0 / nbo) * (nbo * nbo) : c->dKinv + o0 + o0 * ld;
-                g.ldb = overlap ? nbo : ld;
-                g.m = o0;
-                g.n = pw;
-                g.k = pw;
-                g.overwrite = 1;
-                if (overlap)
-                    g.stop_event = ev((size_t)(o0 / nbo)); // this launch's own completion: panel p of U is final
-                PhaseScope ps(c, GPE_PH_INV, gemm_flops(g));
-                launch_gemm_sub(s, g);
-                if (overlap) {
-                    hipStreamWaitEvent(c->stream2, ev((size_t)(o0 / nbo)), 0);
-                    rank_update(c->stream2, o0, pw);
-                }
-            }
-            if (oe < N) {
-                GemmArgs g{};
-                g.C = c->dKinv + oe * ld;
-                g.ldc = ld;
-                g.A = c->dLinv + o0 * ld;
-                g.lda = ld;
-                g.B = c->dA + oe + o0 * ld;
-                g.ldb = ld;
-                g.m = oe;
-                g.n = N - oe;
-                g.k = pw;
-                PhaseScope ps(c, GPE_PH_INV, gemm_flops(g));
-                launch_gemm_sub(s, g);
-            }
-        }
-        if (overlap) {
-            hipEventRecord(ev((size_t)npan), c->stream2);
-            hipStreamWaitEvent(s, ev((size_t)npan), 0);
-        }
-        else {
-            // K^-1 = U U^T (gp.hpp:261) in one launch, lower triangle, k from the tile diagonal on (U is upper
-            // triangular).
-            GemmArgs g{};
-            g.C = c->dKinv;
-            g.ldc = ld;
-            g.A = c->dLinv;
-            g.lda = ld;
-            g.B = c->dLinv;
-            g.ldb = ld;
-            g.m = g.n = g.k = N;
-            g.tri = 1;
-            g.ktri = 1;
-            g.overwrite = 1;
             PhaseScope ps(c, GPE_PH_INV, gemm_flops(g));
             launch_gemm_sub(s, g);
         }
     }
+    if (overlap) {
+        hipEventRecord(ev((size_t)npan), c->stream2);
+        hipStreamWaitEvent(s, ev((size_t)npan), 0);
+    }
     else {
-        {
-            PhaseScope ps(c, GPE_PH_INV, 0.0);
-            launch_set_identity(s, c->dLinv, ld, N);
-        }
-        trsm_left_blocked(c, c->dA, c->dLinv, ld, N, N, true, GPE_PH_INV); // L^-1 (gp.hpp:260)
-        // K^-1 = L^-T L^-1 (gp.hpp:261), lower triangle, k range from the tile diagonal down
+        // K^-1 = U U^T (gp.hpp:261) in one launch, lower triangle, k from the tile diagonal on (U is upper
+        // triangular).
         GemmArgs g{};
         g.C = c->dKinv;
         g.ldc = ld;
         g.A = c->dLinv;
         g.lda = ld;
-        g.a_kmajor = 1;
         g.B = c->dLinv;
         g.ldb = ld;
-        g.b_kmajor = 1;
         g.m = g.n = g.k = N;
         g.tri = 1;
         g.ktri = 1;

@@ -91,7 +91,7 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     digest_kernel(c);
     const int64_t N = c->N;
     const int P = c->P;
-    // Fewer samples than one outer panel (or a panel width the transposed layout does not serve): the N x M layout of
+    // Fewer samples than one outer panel: the N x M layout of
     // query_impl — Z = L^-1 Ks by the blocked solve, k-contiguous operands — and the composed covariance path only
     const bool transposed = qt_serves(c); // (GPE_QUERY_T is not asked here)
     const bool want_cov = cov != nullptr || dr != nullptr;

@@ -1175,7 +1175,9 @@ int debug_tail_order(int nt, int nb, int lag, int pair)
 // Tile columns t0 .. t1-1 (whole 64-blocks) of the rows t0 .. M-1: N64 - t0 full row strips (N64 = the matrix order rounded down
 // to 64; t1 == N64: the closing launch) and, as one more row strip, the M - N64 <= 64 rows below them — right-hand-side rows and
 // the rows of a ragged last block the caller finishes.  Fully updated by everything in front of t0.  buf_cur / buf_next:
-// tail_buf_doubles(nt, nb) each, all-ones (this launch arms buf_next)
+// tail_buf_doubles(nt, nb) each, all-ones (this launch arms buf_next).  gen: the launch generates its tiles of K — only ever
+// given with t0 = 0 and t1 = N64, the launch that is the whole factorisation; what k_tail_g carries for a tall launch
+// (t1 < N64) is no longer reached and leaves with the next change to that kernel
 void launch_tail(hipStream_t s, double* A, int64_t lda, int64_t t0, int64_t t1, int64_t N64, int64_t M, double* Xt_all, int* info,
                  double* buf_cur, double* buf_next, const TailGen* gen)
 {
@@ -1197,8 +1199,7 @@ void launch_tail(hipStream_t s, double* A, int64_t lda, int64_t t0, int64_t t1, 
     // measured (profiles/r04_dispatch_order.log, N = 4096): lag 2..4 -> 794-800 evaluations/s against 735 column by column; a
     // just-in-time window W > 0 LOSES (6: 675, 8: 694, 12: 738, 16: 770): a tile dispatched late has its catch-up products still
     // to do when its row's diagonal workgroup asks for it; waiting workgroups are not what limits the closing launch
-    static const int ord_lag = (int)env_int("GPE_TAIL_LAG", 3);
-    a.order = tail_order(a.nt, a.nb, g_batch.bt ? 0 : TAIL_DLEAD, ord_lag);
+    a.order = tail_order(a.nt, a.nb, g_batch.bt ? 0 : TAIL_DLEAD, /* lag */ 3);
     const int64_t tiles = tail_tiles(a.nt, a.nb);
     if (gen) {
         a.Xg = gen->Xg;

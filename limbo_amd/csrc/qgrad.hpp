@@ -39,7 +39,7 @@ static void qg_extra(const gpe_ctx* c, int nseg, int64_t ldq, int64_t mc_max, si
 static void qt_backward(gpe_ctx* c, const QtBufs& b, int64_t mc)
 {
     hipStream_t s = c->stream;
-    const int64_t N = c->N, ld = c->ld, nbo = c->nbo, ldq = b.ldq;
+    const int64_t N = c->N, ld = c->ld, nbo = NBO, ldq = b.ldq;
     // Wt = Zt L^-1, from the last outer panel to the first; Zt is the running right-hand side (destroyed), Wt goes where
     // Kst was (b.dKst):
     //   Wt[:, p]        = Acc[:, p] X_p                       X_p = inv(L_pp) (qt_panels), untransposed this time

@@ -19,7 +19,7 @@
 // Which layout.  The transposed one serves a context whose outer panels are what the one-launch panel inverses take (inv.hip) and
 // that has at least one of them; the marginal calls (query, gradients, path sets) also obey GPE_QUERY_T, read once per process.
 // The joint posterior and the sparse model ask qt_serves alone; the blocked append goes point by point while it is false.
-static bool qt_serves(const gpe_ctx* c) { return c->nbo % 128 == 0 && c->nbo <= 256 && c->N >= c->nbo; }
+static bool qt_serves(const gpe_ctx* c) { return c->N >= NBO; }
 static bool qt_enabled(const gpe_ctx* c)
 {
     static const bool allowed = env_not_zero("GPE_QUERY_T");
@@ -56,7 +56,7 @@ struct QtBufs {
 static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols, int64_t N_ = -1)
 {
     QtBufs b;
-    const int64_t N = N_ >= 0 ? N_ : c->N, nbo = c->nbo;
+    const int64_t N = N_ >= 0 ? N_ : c->N, nbo = NBO;
     const int D = c->D, P = c->P;
     b.mc_max = mc_max;
     b.ldq = mc_max + 16; // not a power of two (HBM channel camping on column strides), even, 16-byte rows
@@ -86,7 +86,7 @@ static void qt_carve(QtBufs& b, double* base)
     b.dVar = b.dKta + b.n_kta;
     b.dKvv = b.dVar + b.mc_max;
 }
-// The N x M layout in the same buffers — fewer samples than one outer panel, a panel width the transposed layout does not serve,
+// The N x M layout in the same buffers — fewer samples than one outer panel,
 // GPE_QUERY_T=0, caller-supplied cross kernels: Kst holds Ks (ld x mc_max, the samples contiguous) and is solved in place
 // (trsm_left_blocked); no panel inverses, no partial sums; second: Zt is another matrix of that shape, else empty
 static QtBufs nm_layout(const gpe_ctx* c, int64_t mc_max, bool second)
@@ -169,14 +169,14 @@ struct Marks {
 static void qt_panels(gpe_ctx* c, const QtBufs& b)
 {
     PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-    launch_inv_panels(c->stream, c->dA, c->ld, c->N, (int)c->nbo, c->dXinv, b.dXp, 0, nullptr, 0);
+    launch_inv_panels(c->stream, c->dA, c->ld, c->N, NBO, c->dXinv, b.dXp, 0, nullptr, 0);
 }
 // Dst = Src F^-T panel by panel (gp.hpp:620, transposed) for the mc rows of Src, on c's stream and in c's phases; F: the factor of
 // context f — c itself, or another of c's device (the sparse model's Lm) — and X its compact panel inverses.  Src is destroyed.
 static void qt_forward(gpe_ctx* c, const QtBufs& b, int64_t mc, const gpe_ctx* f, const double* X, double* Src, double* Dst)
 {
     hipStream_t s = c->stream;
-    const int64_t N = f->N, ld = f->ld, nbo = f->nbo, ldq = b.ldq;
+    const int64_t N = f->N, ld = f->ld, nbo = NBO, ldq = b.ldq;
     for (int64_t o0 = 0; o0 < N; o0 += nbo) {
         const int64_t pw = std::min<int64_t>(nbo, N - o0), oe = o0 + pw;
         {

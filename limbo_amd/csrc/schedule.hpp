@@ -5,8 +5,8 @@
 
 // ---------------------------------------------------------------------------------------------
 // Blocked right-looking Cholesky, two levels (replaces Eigen::LLT at gp.hpp:565):
-//   outer panels of `nbo` columns: the trailing update runs with k = nbo so that the matrix-core
-//   kernel reads/writes C once per 2*nbo flops per element (k = 64 would be C-traffic bound);
+//   outer panels of NBO columns: the trailing update runs with k = NBO so that the matrix-core
+//   kernel reads/writes C once per 2*NBO flops per element (k = 64 would be C-traffic bound);
 //   inside a panel: 64-column steps  [k_diag: factor + invert | L21 = A21 X^T | in-panel update],
 //   the last two being calls of the same matrix-core kernel.
 // M >= N rows take part (rows N..M-1 = right-hand sides: they come out as (L^-1 b)^T).
@@ -21,7 +21,6 @@ struct TailPlan {
 static TailPlan tail_plan(const gpe_ctx* c, int64_t N, int64_t M)
 {
     TailPlan pl;
-    const int64_t nbo = c->nbo;
     pl.N64 = N / NB * NB;
     // Batched launches (k_tail_b: the members' tiles interleaved in one grid) take the data-flow launches only while all
     // members' tiles together stay within ~18 rounds of the chip: every member has 256 / G resident workgroups, and a tile
@@ -31,9 +30,9 @@ static TailPlan tail_plan(const gpe_ctx* c, int64_t N, int64_t M)
     int64_t tmax = g_batch.bt ? c->batch_tail_max : c->tail_max;
     if (!g_batch.bt && tmax >= 2 * NB && pl.N64 <= c->tail_single)
         tmax = std::max(tmax, pl.N64);
-    if (!(tmax >= 2 * NB && c->panel256 && c->fuse_panel && c->panel_handover && nbo == 4 * NB && M - pl.N64 <= NB))
+    if (!(tmax >= 2 * NB && c->panel256 && c->fuse_panel && c->panel_handover && M - pl.N64 <= NB))
         return pl;
-    const int64_t t0 = pl.N64 > tmax ? (pl.N64 - tmax + nbo - 1) / nbo * nbo : 0;
+    const int64_t t0 = pl.N64 > tmax ? (pl.N64 - tmax + NBO - 1) / NBO * NBO : 0;
     if (pl.N64 - t0 < 2 * NB)
         return pl;
     const int64_t rs = M > pl.N64 ? 1 : 0;
@@ -87,7 +86,7 @@ static void debug_tail_plan(int64_t N, int P, int G, int64_t tail_max, int64_t t
     out[4] = pl.nt_tall;
     out[5] = pl.nb_tall;
     out[6] = pl.N64;
-    out[7] = c.nbo;
+    out[7] = NBO;
 }
 // The hand-over buffers of handle c for this plan, on stream s (ordered in front of the launches that poll them).
 // like != nullptr (a batched launch built from `like`'s pointers): same capacities and the same armed parity as that handle.
@@ -194,14 +193,13 @@ static hipEvent_t nth_event(std::vector<hipEvent_t>& evs, size_t i)
     return evs[i];
 }
 
-// One outer panel, columns [p0, p0 + nbo) (fewer at the end): factored, then its trailing update.  stop0: where the panels
+// One outer panel, columns [p0, p0 + NBO) (fewer at the end): factored, then its trailing update.  stop0: where the panels
 // end in front of a data-flow launch (< 0: nowhere) — the panel in front of it updates everything left in one piece.
 static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0, int64_t stop0, PotrfCarry& cy)
 {
     hipStream_t s = c->stream;
     const int64_t ld = c->ld;
-    const int64_t nbo = c->nbo;
-    const int64_t pw = std::min<int64_t>(nbo, N - p0);
+    const int64_t pw = std::min<int64_t>(NBO, N - p0);
     const int64_t pe = p0 + pw;
     bool diag_done = cy.next_diag_done; // the previous fused step (or fused update) already factored this diagonal block
     cy.next_diag_done = false;
@@ -210,25 +208,24 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
     // head-tile scratch, two halves by panel parity: the copy into A is off the critical path
     // (nothing before the end of the factorisation reads those tiles of A) and may still be
     // pending on the second stream while the next panel is factored
-    double* const Hbase = c->dHead + ((p0 / nbo) & 1) * (32 * NB * NB);
+    double* const Hbase = c->dHead + ((p0 / NBO) & 1) * (32 * NB * NB);
     // Will the trailing update of this panel be the fused launch that also factors the next panel's first
     // diagonal block (k_upd_fused)?  Then the steps of this panel pre-apply their pieces of that block.
-    const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + nbo, N) < N && c->fuse_panel && c->fuse_diag
-        && c->stop_events && pw == nbo && nbo % NB == 0 && nbo >= 2 * NB && ld % 2 == 0
-        && std::min<int64_t>(nbo, N - pe) % NB == 0 && pe != stop0;
+    const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + NBO, N) < N && c->fuse_panel && c->fuse_diag
+        && c->stop_events && pw == NBO && ld % 2 == 0 && std::min<int64_t>(NBO, N - pe) % NB == 0 && pe != stop0;
     // the whole panel in one launch (potrf_panel.hip: k_panel256): full 256 columns, head tiles and block inverses handed over
     // between its workgroups
-    const bool p256 = c->panel256 && c->fuse_panel && c->panel_handover && !g_batch.bt && nbo == 4 * NB && pw == nbo && pe <= M;
+    const bool p256 = c->panel256 && c->fuse_panel && c->panel_handover && !g_batch.bt && pw == NBO && pe <= M;
     // In the first panels of a large factorisation the look-ahead stream is the longer one (N = 4096, panel 1: near + far
     // update 30 + 84 us against 54 + 18 us of chain) and the fused next-panel update, whose 155 KB workgroups need whole CUs,
     // ends up queued behind the far update of the panel before: releasing the stream when the PANEL is complete — its
     // updates need nothing from the fused update — starts every near/far pair one fused update earlier.
     hipEvent_t p_done = nullptr;
-    if (p256 && fuse_diag && c->early_bulk >= 0) {
-        const int64_t pe2_ = std::min<int64_t>(pe + nbo, N), pe3_ = std::min<int64_t>(pe2_ + nbo, N);
+    if (p256 && fuse_diag) {
+        const int64_t pe2_ = std::min<int64_t>(pe + NBO, N), pe3_ = std::min<int64_t>(pe2_ + NBO, N);
         const int64_t nt128 = (N - pe3_ + 127) / 128, far_tiles = nt128 * (nt128 + 1) / 2;
-        if (pe3_ < N && far_tiles >= c->early_bulk)
-            p_done = nth_event(c->pl_events, (size_t)(p0 / nbo));
+        if (pe3_ < N && far_tiles >= 100) // (128 x 128 tiles of the far update)
+            p_done = nth_event(c->pl_events, (size_t)(p0 / NBO));
     }
     if (p256) {
         double* Xt = c->dXinv + (p0 / NB) * (NB * NB);
@@ -262,11 +259,10 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             // scratch sum (the second step starts it); the third — whose workgroup there has the most slack —
             // also the first step's piece
             const bool pre = fuse_diag && j0 > p0;
-            const int64_t dfirst_at = nbo >= 3 * NB ? p0 + 2 * NB : p0 + NB;
             launch_panel_step(s, A, ld, j0, M, nt, Xt, Xt + NB * NB, nt > 0 ? 1 : 0, c->dInfo, Hbase + htile * NB * NB,
-                              pre ? pe : -1, pre && j0 == dfirst_at ? p0 : -1, j0 == p0 + NB ? 1 : 0,
+                              pre ? pe : -1, pre && j0 == p0 + 2 * NB ? p0 : -1, j0 == p0 + NB ? 1 : 0,
                               c->dHead + 64 * NB * NB,
-                              c->panel_handover ? (gpe_epoch_t*)(c->dHead + 65 * NB * NB) + ((p0 / nbo) & 1) * 32 + htile : nullptr);
+                              c->panel_handover ? (gpe_epoch_t*)(c->dHead + 65 * NB * NB) + ((p0 / NBO) & 1) * 32 + htile : nullptr);
             htile += nt;
             if (nt > 0)
                 ++nf;
@@ -312,7 +308,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             PhaseScope ps(c, GPE_PH_POTRF_UPDATE, gemm_flops(g));
             launch_gemm_sub(st, g);
         };
-        const int64_t pe2 = std::min<int64_t>(pe + nbo, N);
+        const int64_t pe2 = std::min<int64_t>(pe + NBO, N);
         if (c->lookahead && !c->prof && pe2 < N && pe != stop0) {
             // look-ahead: the next panel's columns are updated on the main stream, the rest of the
             // trailing matrix on the second stream while the next panel is factored
@@ -322,7 +318,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             // finished the columns of panel kp + 2 ("near" part, done first), 3 kp + 2 = all of it.
             // The main stream only ever waits for a near part, which completed most of a panel earlier:
             // waiting for an event that fires just in time cost ~10 us per panel in the kernel trace.
-            const size_t kp = (size_t)(p0 / nbo);
+            const size_t kp = (size_t)(p0 / NBO);
             if (cy.la_pending)
                 hipStreamWaitEvent(s, ev(3 * (kp - 1) + 1), 0); // the previous bulk update also wrote these columns
             if (fuse_diag) {
@@ -344,7 +340,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             hipStreamWaitEvent(c->stream2, p_done ? p_done : ev(3 * kp), 0); // the bulk update starts now and shares the
                                                            // chip with panel kp + 1 only (p_done: and with this update)
             head_copy(c->stream2);
-            const int64_t pe3 = std::min<int64_t>(pe2 + nbo, N);
+            const int64_t pe3 = std::min<int64_t>(pe2 + NBO, N);
             upd(c->stream2, pe2, pe3, pe2); // near: what panel kp + 1's update needs
             hipEventRecord(ev(3 * kp + 1), c->stream2);
             if (pe3 < N) // far: dispatched unrestricted, the panel's workgroups take CUs as tiles retire (holding CUs back for
@@ -367,7 +363,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
 }
 
 // The tall data-flow launch over [e0, t0), every row strip below riding along, and its ONE update of everything behind t0.
-static void potrf_tall(gpe_ctx* c, double* A, int64_t M, const TailPlan& pl, const TailGen& gen, PotrfCarry& cy)
+static void potrf_tall(gpe_ctx* c, double* A, int64_t M, const TailPlan& pl, PotrfCarry& cy)
 {
     hipStream_t s = c->stream;
     const int64_t ld = c->ld, e0 = pl.e0, t0 = pl.t0, N64 = pl.N64;
@@ -377,9 +373,7 @@ static void potrf_tall(gpe_ctx* c, double* A, int64_t M, const TailPlan& pl, con
         PhaseScope ps(c, GPE_PH_POTRF_TALL, w * w * w / 3.0 + (h - w) * w * w);
         double* pair = c->dTail + 2 * c->tail_cap;
         launch_tail(s, A, ld, e0, t0, N64, M, c->dXinv, c->dInfo, pair + (c->tall_count & 1) * c->tall_cap,
-                    pair + ((c->tall_count + 1) & 1) * c->tall_cap, c->gen_mode == 2 ? &gen : nullptr);
-        if (c->gen_mode == 2 && c->gen_ev) // the rest of K, built on the second stream beside this launch
-            hipStreamWaitEvent(s, c->gen_ev, 0);
+                    pair + ((c->tall_count + 1) & 1) * c->tall_cap);
         ++c->tall_count;
         c->tall_lay = pl.nt_tall * 65536 + pl.nb_tall;
     }
@@ -406,7 +400,7 @@ static bool potrf_closing(gpe_ctx* c, double* A, int64_t N, int64_t M, const Tai
     {
         PhaseScope ps(c, GPE_PH_POTRF_TAIL, (double)(N64 - t0) * (N64 - t0) * (N64 - t0) / 3.0);
         launch_tail(s, A, ld, t0, N64, N64, M, c->dXinv, c->dInfo, c->dTail + (c->tail_count & 1) * c->tail_cap,
-                    c->dTail + ((c->tail_count + 1) & 1) * c->tail_cap, c->gen_mode == 1 ? &gen : nullptr);
+                    c->dTail + ((c->tail_count + 1) & 1) * c->tail_cap, c->gen_mode ? &gen : nullptr);
         ++c->tail_count;
         c->tail_lay = pl.nt_tail * 65536 + pl.nb_tail;
     }
@@ -419,11 +413,9 @@ static bool potrf_closing(gpe_ctx* c, double* A, int64_t N, int64_t M, const Tai
     // buffers the closing launch has just used — dead until the next launch arms all of them again
     double* const used = c->dTail + ((c->tail_count - 1) & 1) * c->tail_cap;
     // ... and factored, inverted and its right-hand-side rows solved by the same two launches where that form serves
-    // (GPE_RAGGED_FINISH=0: the update alone, then the panel code)
-    static const bool finish = env_not_zero("GPE_RAGGED_FINISH");
     // (one workgroup adds the slots up here: worth it while the block is narrow — N = 520 0.156 -> 0.149 ms, 1100 0.269 ->
     // 0.258; from ~40 columns on the sixteen workgroups of k_ragged_fold are quicker than the launches they cost)
-    if (finish && !c->prof && N - N64 <= 40
+    if (!c->prof && N - N64 <= 40
         && launch_ragged_finish(s, g.C, ld, g.A, ld, N - N64, M - N, g.k, used, pl.need_tail, c->dXinv + (N64 / NB) * (NB * NB),
                                 c->dInfo, N64))
         return true;
@@ -443,13 +435,13 @@ void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M, const TailPlan& 
 {
     PotrfCarry cy;
     const int64_t stop0 = pl.e0 >= 0 ? pl.e0 : pl.t0; // where the panels end in front of a data-flow launch (< 0: at N)
-    for (int64_t p0 = 0; p0 < (stop0 >= 0 ? stop0 : N); p0 += c->nbo)
+    for (int64_t p0 = 0; p0 < (stop0 >= 0 ? stop0 : N); p0 += NBO)
         potrf_panel(c, A, N, M, p0, stop0, cy);
     if (pl.t0 >= 0) {
-        // gen_mode (compute_enqueue): the first data-flow launch generates its tiles of K itself — nobody built them
+        // gen_mode (compute_enqueue): the launch that is the whole factorisation generates its tiles of K itself — nobody built them
         const TailGen gen{c->dXt, c->ld, N, c->dOm, c->ld, (c->flow_solve && (N + NB - 1) / NB <= 256) ? c->dAl : nullptr, c->ld, c->P, &c->kp};
         if (pl.e0 >= 0)
-            potrf_tall(c, A, M, pl, gen, cy);
+            potrf_tall(c, A, M, pl, cy);
         if (!potrf_closing(c, A, N, M, pl, gen, cy))
             potrf_panel(c, A, N, M, pl.N64, stop0, cy);
     }
@@ -463,9 +455,8 @@ void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int6
 {
     hipStream_t s = c->stream;
     const int64_t ld = c->ld;
-    const int64_t nbo = c->nbo;
-    for (int64_t o0 = 0; o0 < N; o0 += nbo) {
-        const int64_t ow = std::min<int64_t>(nbo, N - o0);
+    for (int64_t o0 = 0; o0 < N; o0 += NBO) {
+        const int64_t ow = std::min<int64_t>(NBO, N - o0);
         const int64_t oe = o0 + ow;
         for (int64_t j0 = o0; j0 < oe; j0 += NB) {
             const int jb = (int)std::min<int64_t>(NB, oe - j0);
@@ -529,10 +520,9 @@ void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int6
 // shape — the caller takes k_trsv_bwd_flow
 static bool bwd_chain_sweep(gpe_ctx* c, hipStream_t s, const double* y, int64_t ysi, double* al, int prefilled, const double* om, double* part)
 {
-    static const bool on = env_not_zero("GPE_SWEEP_M");
     const int64_t nblk = (c->N + NB - 1) / NB;
     // (below eight blocks the two matrix-core products in front of the chain cost what the shorter hops save: N = 256 0.077 against 0.075 ms)
-    if (!on || g_batch.bt || g_batch.G != 1 || nblk < 8 || nblk > 256)
+    if (g_batch.bt || g_batch.G != 1 || nblk < 8 || nblk > 256)
         return false;
     launch_trsv_bwd_m(s, c->dA, c->ld, c->N, c->dXinv, y, ysi, al, c->dInfo + 1, prefilled, om, part);
     return true;
@@ -643,63 +633,38 @@ int compute_enqueue(gpe_ctx* c)
     const bool flow_al = c->flow_solve && (c->N + NB - 1) / NB <= 256;
     bool rows_done = false; // obs_mean^T under the matrix + the sweep's sentinel: by the build launch itself where it can
     // Round 4: where the data-flow launches begin decides whether K is built at all.  When the first of them starts at
-    // column 0 it generates its tiles itself (potrf_tail.hip: tail_gen_tile): for N <= 2560 the kernel matrix is never written,
-    // for the tall launch of N = 4096 only the 2560 x 2560 block behind it is — beside the tall launch, on the second stream.
-    // GPE_TAIL_GEN: 0 never; 1 (default) when ONE launch is the whole factorisation (N <= 2560: 0.489 -> 0.477 ms at
-    // N = 2048, 0.254 -> 0.247 at 1024); 2 / 3: also the tall launch of N <= 4096, the block behind it built on the second
-    // stream beside it / on the main stream in front of it — measured at N = 4096: 2 LOSES (1.253 -> 1.272 ms: the build
-    // takes CUs from the first columns of the chain and the update then waits for an event)
-    static const int gen_lvl = (int)env_int("GPE_TAIL_GEN", 1);
-    c->gen_mode = 0;
-    if (gen_lvl > 0 && !c->host_K && !c->prof && pl.t0 >= 0) {
-        if (pl.t0 == 0 && (c->N % NB == 0 || !g_batch.bt))
-            c->gen_mode = 1;
-        else if (pl.e0 == 0 && !g_batch.bt && gen_lvl >= 2)
-            c->gen_mode = 2;
-    }
+    // column 0 AND is the whole factorisation it generates its tiles itself (potrf_tail.hip: tail_gen_tile): the kernel matrix
+    // is never written (0.489 -> 0.477 ms at N = 2048, 0.254 -> 0.247 at 1024).  GPE_TAIL_GEN=0: K is always built.  (The tall
+    // launch generating its tiles, the block behind it built beside it, was measured at N = 4096 and LOST, 1.253 -> 1.272 ms:
+    // the build takes CUs from the first columns of the chain and the update then waits for an event.)
+    static const bool gen_ok = env_not_zero("GPE_TAIL_GEN");
+    c->gen_mode = gen_ok && !c->host_K && !c->prof && pl.t0 == 0 && (c->N % NB == 0 || !g_batch.bt);
     if (c->host_K) {
         if (!c->dKhost)
             return GPE_ERR_STATE;
         PhaseScope ps(c, GPE_PH_KERNEL_BUILD, 0.0);
         launch_copy2d(s, c->dKhost, c->ld, c->dA, c->ld, c->N, c->N);
     }
-    else if (c->gen_mode != 0) {
+    else if (c->gen_mode) {
         project_lambda(c, s, c->dXt, c->ld, 0, c->N);
-        // what is left to build: the ragged last block (mode 1) / everything behind the tall launch (mode 2), with
-        // obs_mean's rows and the sweep's sentinel for those columns
-        const int64_t b0 = c->gen_mode == 1 ? c->N / NB * NB : pl.t0;
+        // what is left to build: the ragged last block, with obs_mean's rows and the sweep's sentinel for those columns
+        const int64_t b0 = c->N / NB * NB;
         rows_done = true;
         if (b0 < c->N) {
             const BuildRowsTail rt{c->dOm + b0, c->ld, c->P, c->dA + c->N + b0 * c->ld, flow_al ? c->dAl + b0 : nullptr, 0};
-            hipStream_t sb = s;
-            if (c->gen_mode == 2 && c->kp.k_lam == 0 && gen_lvl != 3) { // beside the tall launch (nothing of this handle is in flight on stream2)
-                sb = c->stream2;
-                if (!c->gen_ev)
-                    hipEventCreateWithFlags(&c->gen_ev, hipEventDisableTiming);
-            }
-            if (!launch_build_K(sb, c->dXt + b0, c->ld, c->N - b0, c->kp, c->dA + b0 + b0 * c->ld, c->ld, &rt))
-                launch_cols_to_rows(sb, c->dOm + b0, c->ld, c->N - b0, c->P, c->dA + c->N + b0 * c->ld, c->ld, flow_al ? c->dAl + b0 : nullptr);
-            if (sb != s)
-                hipEventRecord(c->gen_ev, sb);
-            else if (c->gen_ev) { // (mode 2 on the main stream: no event to wait for)
-                hipEventDestroy(c->gen_ev);
-                c->gen_ev = nullptr;
-            }
+            if (!launch_build_K(s, c->dXt + b0, c->ld, c->N - b0, c->kp, c->dA + b0 + b0 * c->ld, c->ld, &rt))
+                launch_cols_to_rows(s, c->dOm + b0, c->ld, c->N - b0, c->P, c->dA + c->N + b0 * c->ld, c->ld, flow_al ? c->dAl + b0 : nullptr);
         }
-        c->al_prefilled = flow_al;
     }
     else {
         PhaseScope ps(c, GPE_PH_KERNEL_BUILD, 0.0);
         project_lambda(c, s, c->dXt, c->ld, 0, c->N);
         const BuildRowsTail rt{c->dOm, c->ld, c->P, c->dA + c->N, flow_al ? c->dAl : nullptr, 0};
-        static const bool tail = env_not_zero("GPE_ROWS_TAIL");
-        rows_done = launch_build_K(s, c->dXt, c->ld, c->N, c->kp, c->dA, c->ld, tail ? &rt : nullptr);
+        rows_done = launch_build_K(s, c->dXt, c->ld, c->N, c->kp, c->dA, c->ld, &rt);
     }
-    if (c->gen_mode == 0) {
-        if (!rows_done)
-            launch_cols_to_rows(s, c->dOm, c->ld, c->N, c->P, c->dA + c->N, c->ld, flow_al ? c->dAl : nullptr);
-        c->al_prefilled = flow_al;
-    }
+    if (!rows_done)
+        launch_cols_to_rows(s, c->dOm, c->ld, c->N, c->P, c->dA + c->N, c->ld, flow_al ? c->dAl : nullptr);
+    c->al_prefilled = flow_al;
     potrf_blocked(c, c->dA, c->N, c->N + c->P, pl);
     c->have_L = true;
     c->inv_ok = false; // gp.hpp:570

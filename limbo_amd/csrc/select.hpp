@@ -9,7 +9,7 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
     hipStream_t s = c->stream;
     digest_kernel(c);
     const int64_t N = c->N;
-    // Fewer samples than one outer panel (or a panel width the transposed layout does not serve): the N x M layout of query_impl,
+    // Fewer samples than one outer panel: the N x M layout of query_impl,
     // transposed once into the layout of the rounds
     const bool transposed = qt_serves(c);
     int cus = 256;

@@ -281,9 +281,9 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     HIPCHK(h, hipMemsetAsync(dZero, 0, sizeof(double) * (size_t)mc_max, s));
     if (transposed) {
         qt_panels(in, b);
-        const int64_t npan = (M + sc->nbo - 1) / sc->nbo;
-        HIPCHK(h, h->dXp2.reserve((size_t)(npan * sc->nbo * sc->nbo)));
-        launch_inv_panels(s, sc->dA, sc->ld, M, (int)sc->nbo, sc->dXinv, h->dXp2, 0, nullptr, 0);
+        const int64_t npan = (M + NBO - 1) / NBO;
+        HIPCHK(h, h->dXp2.reserve((size_t)(npan * NBO * NBO)));
+        launch_inv_panels(s, sc->dA, sc->ld, M, NBO, sc->dXinv, h->dXp2, 0, nullptr, 0);
     }
     int rc = GPE_OK;
     for (int64_t t0 = 0; t0 < T && rc == GPE_OK; t0 += mc_max) {

@@ -93,6 +93,21 @@ def test_binding_loads_engine_without_gpu():
     assert lib.prefix == "gpe_"
 
 
+def test_switches_document_lists_exactly_the_names_the_product_reads():
+    """SWITCHES.md opens with "every getenv of the product": the names in the first column of its table are the names read
+    through getenv / std::getenv / env_int / env_flag / env_not_zero in limbo_amd/csrc and include/limbo_amd, no more, no fewer."""
+    files = [p for p in (ROOT / "limbo_amd" / "csrc").iterdir() if p.suffix in (".hip", ".h", ".hpp")]
+    files += [p for p in (ROOT / "include" / "limbo_amd").rglob("*") if p.suffix in (".h", ".hpp")]
+    assert len(files) > 40
+    read = set()
+    for p in files:
+        read |= set(re.findall(r'\b(?:getenv|env_int|env_flag|env_not_zero)\s*\(\s*"([A-Za-z0-9_]+)"', p.read_text()))
+    rows = re.findall(r"^\|\s*`([A-Za-z0-9_]+)`\s*\|", (ROOT / "SWITCHES.md").read_text(), flags=re.M)
+    assert len(rows) == len(set(rows)), sorted(n for n in set(rows) if rows.count(n) > 1)
+    assert read == set(rows), (sorted(read - set(rows)), sorted(set(rows) - read))
+    assert len(rows) > 30  # (the patterns still find them)
+
+
 def test_dispatch_tables_of_the_data_flow_launches_are_deadlock_free():
     """csrc/potrf_tail.hip: tail_order.  A data-flow launch (k_tail) is deadlock-free because every workgroup waits for
     lower-numbered ones only; the order is a TABLE (diagonal workgroups early, tiles below the triangle lagging the chain).

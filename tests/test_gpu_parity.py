@@ -46,10 +46,12 @@ def test_gpu_kernel_matrix_vs_oracle(engine_lib, oracle_lib, kind):
 
 @pytest.mark.parametrize("N,D,P,kind", [(1, 2, 1, O.SE_ARD), (63, 3, 1, O.SE_ARD), (64, 3, 2, O.MATERN52),
                                         (65, 1, 1, O.SE_ARD), (257, 6, 3, O.SE_ARD), (700, 12, 1, O.MATERN52),
-                                        (1100, 6, 2, O.SE_ARD)])
+                                        (1100, 6, 2, O.SE_ARD), (1086, 3, 3, O.SE_ARD)])
 def test_gpu_vs_oracle_full_path(engine_lib, oracle_lib, N, D, P, kind):
     """compute / log-lik / grad / query against the oracle on identical inputs, including
-    block-edge sizes (63, 64, 65, 257: the 64-column and 256-column panel boundaries)."""
+    block-edge sizes (63, 64, 65, 257: the 64-column and 256-column panel boundaries) and an order whose ragged block and
+    obs_mean's rows do not fit one 64-row strip (1086 = 1024 + 62, P = 3: no data-flow launch — look-ahead panels to the
+    end, whose far updates have a handful of tiles and do not release the second stream early)."""
     rng = np.random.default_rng(N * 7 + D)
     X = rng.uniform(0, 1, size=(N, D))
     Y = np.stack([np.cos((p + 1) * X.sum(axis=1)) + 0.05 * rng.normal(size=N) for p in range(P)], axis=1)
@@ -487,13 +489,13 @@ def _small_parity(engine_lib, oracle_lib, N=300, D=3, P=2, seed=0):
 
 
 @pytest.mark.parametrize("env", [{"GPE_FLOW_SOLVE": "0"}, {"GPE_LOOKAHEAD": "0"}, {"GPE_FUSE_PANEL": "0"},
-                                 {"GPE_FUSE_DIAG": "0", "GPE_STOP_EVENT": "0"}, {"GPE_NBO": "192"},
-                                 {"GPE_PANEL256": "0"}, {"GPE_TAIL_MAX": "0"}, {"GPE_TALL": "0"}, {"GPE_TAIL_LAG": "0"}],
+                                 {"GPE_FUSE_DIAG": "0", "GPE_STOP_EVENT": "0"},
+                                 {"GPE_PANEL256": "0"}, {"GPE_TAIL_MAX": "0"}, {"GPE_TALL": "0"}],
                          ids=lambda e: "+".join(f"{k}={v}" for k, v in e.items()))
 def test_gpu_alternate_schedules(engine_lib, oracle_lib, monkeypatch, env):
     """The switches read when a handle is created select the schedules that also serve as fall-backs (per-block
-    sweeps beyond 256 blocks, one stream, unfused panel steps, a panel width the block-inverse path does not
-    take): each must give the oracle's results too.  N = 520: three outer panels, ragged last block."""
+    sweeps beyond 256 blocks, one stream, unfused panel steps, panels instead of the data-flow launches): each must give
+    the oracle's results too.  N = 520: three outer panels, ragged last block."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     _small_parity(engine_lib, oracle_lib, N=520, seed=len(env))
@@ -508,24 +510,21 @@ def _switch_memo_dir(tmp_path_factory):
     return _SWITCH_MEMO[0]
 
 
-@pytest.mark.parametrize("env", [{"GPE_QUERY_SWEEP": "0", "GPE_INV_PANELS": "0"}, {"GPE_QUERY_T": "0", "GPE_INV_OVERLAP": "0"},
-                                 {"GPE_RHS_FMA": "2"}, {"GPE_RHS_FMA": "0"}, {"GPE_PANEL256": "0", "GPE_TAIL_MAX": "0"}, {"GPE_TAIL_MAX": "0"},
-                                 {"GPE_EARLY_BULK_TILES": "0", "GPE_ROWS_TAIL": "0"},
-                                 {"GPE_INV2": "0"}, {"GPE_HP_FUSED": "0", "GPE_INV2_MIN_N": "256"},
+@pytest.mark.parametrize("env", [{"GPE_QUERY_SWEEP": "0"}, {"GPE_QUERY_T": "0"},
+                                 {"GPE_PANEL256": "0", "GPE_TAIL_MAX": "0"}, {"GPE_TAIL_MAX": "0"},
+                                 {"GPE_INV2": "0"}, {"GPE_INV2_MIN_N": "256"},
                                  {"GPE_FLOW_PARTITIONS": "0", "GPE_FLOW_XCD": "0", "GPE_FLOW_GATE": "0"},
                                  {"GPE_STREAM_PRIO": "0", "GPE_TAIL_GEN": "0", "GPE_TRACE": "1", "GPE_ROCTX": "1"},
-                                 {"GPE_BATCH_SPLIT": "0", "GPE_BATCH_TAIL_TILES": "0", "GPE_BATCH_TAIL_MAX": "512"}, {"GPE_BATCH": "0"},
-                                 {"GPE_SWEEP_M": "0", "GPE_XPROC_LOCK": "0", "GPE_TRI_MAP": "0", "GPE_RAGGED_FINISH": "0"}],
+                                 {"GPE_BATCH_TAIL_TILES": "0", "GPE_BATCH_TAIL_MAX": "512"}, {"GPE_BATCH": "0"},
+                                 {"GPE_XPROC_LOCK": "0"}],
                          ids=lambda e: "+".join(f"{k}={v}" for k, v in e.items()))
 def test_gpu_process_wide_switches(env, tmp_path_factory):
-    """Switches that are read once per process (the blocked point-query solve, the in-panel substitution chain for K^-1; round 3:
-    the sample-contiguous batched queries, K^-1's product after its chain, right-hand-side rows always / never as FMAs,
-    the look-ahead stream released by every panel and obs_mean's rows by a launch of their own; round 4: 256-column panels to
-    the end — one-launch (GPE_TAIL_MAX=0) or step by step (+ GPE_PANEL256=0): the schedules the data-flow launches replaced and
-    what a hand-over timeout falls back to; round 5: K^-1 in its panel form instead of the recursion, the objective as
-    separate calls instead of one enqueue, no CU-masked chain partitions / XCD-local sweeps / gate, default stream priorities
-    with K built in front of the one-launch factorisation and the launch trace on, batched sequences unsplit / with the
-    data-flow launches at any size / member by member): the same parity checks in a child, at a size with seven outer
+    """Switches that are read once per process (the blocked point-query solve; round 3: the sample-contiguous batched queries;
+    round 4: 256-column panels to the end — one-launch (GPE_TAIL_MAX=0) or step by step (+ GPE_PANEL256=0): the schedules the
+    data-flow launches replaced and what a hand-over timeout falls back to; round 5: K^-1 in its panel form instead of the
+    recursion, the recursion from N = 256 on, no CU-masked chain partitions / XCD-local sweeps / gate, default stream priorities
+    with K built in front of the one-launch factorisation and the launch trace on, batched sequences with the data-flow
+    launches at any size / member by member; round 6: no lock between processes): the same parity checks in a child, at a size with seven outer
     panels (N = 1700: ragged last panel), for the hyper-parameter objective through gpe_hp_objective (N = 1792: seven panels,
     the recursion's tree is unbalanced), and a batched factorisation (3 x N = 700) and objective (2 x N = 1024) — every
     switch of SWITCHES.md that is not a handle-creation switch (test_gpu_alternate_schedules) is set by one of these."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Config 3 factorisation (N=16384, D=12, Matern-5/2): compute()+log_lik time for the switches given in the environment
-(e.g. GPE_BULK_WGS = workgroups of a look-ahead bulk update; 0 = unlimited).  usage: c3bench.py [N]"""
+(e.g. GPE_TAIL_MAX=0: 256-column panels to the end).  usage: c3bench.py [N]"""
 import sys
 import time
 from pathlib import Path

@@ -3,7 +3,7 @@
 
   python tools/inv2_try.py check            K^-1 and the gradient at N = 1024, 2048, 4096 vs LAPACK (both paths)
   python tools/inv2_try.py time [N]         gpe_hp_objective (gradient) wall time + the `inv` phase, both paths
-The path is chosen per PROCESS (GPE_INV2, GPE_INV2_BINS, GPE_INV2_LOAD are read once): this script re-runs itself.
+The path is chosen per PROCESS (GPE_INV2 is read once): this script re-runs itself.
 """
 import os
 import subprocess
@@ -32,7 +32,7 @@ def child(mode, N):
     rng = np.random.default_rng(N)
     th = rng.uniform(-0.3, 0.3, size=7)
     h.set_kernel(O.SE_ARD, th, 0.01)
-    tag = f"GPE_INV2={os.environ.get('GPE_INV2', '1')} BINS={os.environ.get('GPE_INV2_BINS', '-')} LOAD={os.environ.get('GPE_INV2_LOAD', '-')}"
+    tag = f"GPE_INV2={os.environ.get('GPE_INV2', '1')}"
     if mode == "check":
         assert h.compute() == 0
         g = h.log_lik_grad(False)
@@ -115,8 +115,6 @@ def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "check"
     sizes = [int(a) for a in sys.argv[2:]] or ([1024, 2048, 4096] if mode == "check" else [4096])
     variants = [{"GPE_INV2": "0"}, {"GPE_INV2": "1"}]
-    if mode == "time":
-        variants += [{"GPE_INV2": "1", "GPE_HP_FUSED": "0"}]
     for N in sizes:
         for v in variants:
             env = dict(os.environ, **v)

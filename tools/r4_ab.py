@@ -1,6 +1,6 @@
 """Round-4 schedule A/B on one box: compute()+log_lik at N = 4096 (and other sizes) under different splits between the tall
 data-flow launch, the one update behind it and the closing launch (GPE_TALL / GPE_TAIL_MAX are read per handle), the phase
-times of the default schedule, and the batched forms (GPE_BATCH_TAIL is process-wide: child processes).
+times of the default schedule, and the batched forms (child processes).  tools/refresh_profiles.sh and tools/boxcheck.sh call it.
 
     python tools/r4_ab.py single | phases | sizes | batch [0|1] | all
 """
@@ -66,18 +66,17 @@ def single():
 def single2():
     X, Y = O.make_problem("c2", N=4096)
     om, _ = O.obs_mean_data(Y)
-    tag = " ".join(f"{k}={os.environ[k]}" for k in ("GPE_TAIL_W", "GPE_TAIL_LAG", "GPE_TAIL_W_BATCH") if k in os.environ)
     for tall, tail in [(4096, 2560), (4096, 2816), (0, 2560)]:
         h = handle(X, om, O.SE_ARD, np.zeros(7), tall, tail)
         med, mn, ll = timed(h, steps=20, warm=3)
-        print(f"[{tag}] tall_max {tall:5d} tail_max {tail:5d}: {med:.3f} / {mn:.3f} ms  -> {1e3 / med:7.1f} evaluations/s  log_lik {ll:.12g} reruns {h.flow_retries()}")
+        print(f"tall_max {tall:5d} tail_max {tail:5d}: {med:.3f} / {mn:.3f} ms  -> {1e3 / med:7.1f} evaluations/s  log_lik {ll:.12g} reruns {h.flow_retries()}")
         h.close()
     for N in (2048, 1024):
         X2, Y2 = O.make_problem("c2", N=N)
         om2, _ = O.obs_mean_data(Y2)
         h = handle(X2, om2, O.SE_ARD, np.zeros(7), None, None)
         med, mn, ll = timed(h, steps=20, warm=3)
-        print(f"[{tag}] N {N}: {med:.3f} / {mn:.3f} ms  log_lik {ll:.12g}")
+        print(f"N {N}: {med:.3f} / {mn:.3f} ms  log_lik {ll:.12g}")
         h.close()
 
 
@@ -125,7 +124,7 @@ def sizes():
 
 
 def batch():
-    print(f"# batched launches, GPE_BATCH_TAIL={os.environ.get('GPE_BATCH_TAIL', '1')} GPE_TAIL_MAX={os.environ.get('GPE_TAIL_MAX', '-')} GPE_TALL={os.environ.get('GPE_TALL', '-')}")
+    print(f"# batched launches, GPE_TAIL_MAX={os.environ.get('GPE_TAIL_MAX', '-')} GPE_TALL={os.environ.get('GPE_TALL', '-')}")
     for G, N in (((8, 2048),) if os.environ.get("R4_BATCH8") else ((8, 2048), (64, 2048), (10, 4096))):
         X, Y = O.make_problem("c4" if N == 2048 else "c2", N=N)
         rng = np.random.default_rng(4)
@@ -192,6 +191,6 @@ if __name__ == "__main__":
         med, mn, ll = timed(h, steps=12, warm=3)
         print(f"{1e3 / med:.1f}")
     if what == "all":
-        for env in ({"GPE_BATCH_TAIL": "0"}, {}, {"GPE_TAIL_MAX": "4096"}, {"GPE_TAIL_MAX": "2816"}):
+        for env in ({}, {"GPE_TAIL_MAX": "4096"}, {"GPE_TAIL_MAX": "2816"}):
             r = subprocess.run([sys.executable, __file__, "batch"], env=dict(os.environ, **env), capture_output=True, text=True)
             print(r.stdout + r.stderr[-2000:])

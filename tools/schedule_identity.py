@@ -36,15 +36,12 @@ CASES = {
     "d": (512, 1, {"GPE_TAIL_MAX": "256", "GPE_TALL": "256"}, "tall [0,256), one update, closing"),
     "e": (1300, 3, {"GPE_TAIL_MAX": "256", "GPE_TALL": "0"}, "four look-ahead panels in front of a closing launch, ragged, P = 3"),
     "f": (1700, 1, {"GPE_TAIL_MAX": "0"}, "panels to the end, ragged last panel"),
-    "g": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_EARLY_BULK_TILES": "0"}, "the p_done release"),
     "h": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_PANEL256": "0"}, "fused steps"),
     "i": (1700, 1, {"GPE_TAIL_MAX": "0", "GPE_PANEL256": "0", "GPE_PANEL_HANDOVER": "0"}, "head copy"),
     "j": (520, 1, {"GPE_FUSE_PANEL": "0"}, "the three-launch step"),
     "k": (520, 1, {"GPE_FUSE_DIAG": "0", "GPE_STOP_EVENT": "0"}, "the marker-packet form"),
     "l": (520, 1, {"GPE_LOOKAHEAD": "0"}, "single stream"),
-    "m": (520, 1, {"GPE_NBO": "192"}, "a panel width the block-inverse paths do not take"),
     "n": (520, 1, {"GPE_TAIL_GEN": "0"}, "K built in front of the one-launch factorisation"),
-    "o": (520, 1, {"GPE_RAGGED_FINISH": "0"}, "ragged update, k_diag_full, panel code"),
     "p": (3584, 1, {}, "the default three launches"),
     "q": (3640, 1, {}, "the default three launches, ragged 56"),
     "r": (4608, 1, {}, "default look-ahead panels in front of the closing launch"),
@@ -62,7 +59,6 @@ CASES["lifecycle"] = (300, 2, {}, "one handle through set_data, grow, the query 
 QUERY_CASES = {
     "q64": (520, 70, 0, False, {}, "the transposed layout, 64-tiles, ragged in N and in the points"),
     "q128": (1100, 70, 0, False, {}, "the transposed layout, 128-tiles"),
-    "qnbo": (520, 70, 0, False, {"GPE_NBO": "192"}, "a panel width the transposed layout does not serve: N x M, the by-inverse routes"),
     "qnm": (520, 70, 0, False, {"GPE_QUERY_T": "0"}, "N x M by the switch; the joint posterior stays transposed"),
     "qsub": (200, 70, 0, False, {"GPE_SMALL": "0"}, "fewer samples than one outer panel: N x M"),
     "qfew": (520, 5, 0, False, {}, "a handful of points: the one-launch sweep of query_impl"),
