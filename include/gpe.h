@@ -21,6 +21,13 @@
  *     first non-positive Cholesky pivot (the reference never checks
  *     Eigen::LLT::info(), gp.hpp:565 — the C++ wrapper mirrors that and just
  *     records it); <0 = GPE_ERR_*.
+ *   - after a status j > 0 of a factorising call (gpe_compute, gpe_hp_objective, the batched forms): the leading
+ *     (j-1) x (j-1) triangle of L is the valid factor of K's leading block, nothing is promised about rows or
+ *     columns >= j-1 (0-based), and the log-likelihood is not finite, so an optimiser never gets a number from a
+ *     failed factorisation.  A failing pivot is no hand-off timeout: gpe_flow_retries / gpe_handover_reruns do not
+ *     move.  The next factorisation on the handle is unaffected: with a K that is positive definite it returns 0 and
+ *     the results of a fresh handle, bit for bit.  Appends still append (gpe_nb_samples grows, as in the reference,
+ *     which never looks at the pivot).
  *   - hyper-parameters are in limbo's log-space (kernel/kernel.hpp:104-123).
  *   - one handle = one GP = one HIP stream; different handles may be driven
  *     from different host threads concurrently; const queries on one handle
@@ -112,14 +119,18 @@ int gpe_set_K_host(gpe_handle h, const double* K, int64_t ldk);
 /* ---- the hot path -------------------------------------------------------- */
 /* gp.hpp:550-571 `_compute_full_kernel`: K (kernel build, +noise+1e-8 on the
  * diagonal) -> L = chol(K) (replaces Eigen::LLT, gp.hpp:565) -> alpha
- * (gp.hpp:605-611).  Everything stays in HBM. */
+ * (gp.hpp:605-611).  Everything stays in HBM.  Returns 0, or j = the 1-based index of the
+ * first non-positive pivot: then L's leading (j-1) x (j-1) triangle is valid, gpe_log_lik is
+ * not finite, and the next gpe_compute is unaffected (see Conventions). */
 int gpe_compute(gpe_handle h);
 /* gp.hpp:241-252 recompute(update_obs_mean, false): new obs_mean, same L */
 int gpe_update_alpha(gpe_handle h, const double* obs_mean);
 /* gp.hpp:126-152 + :573-603: append one sample; obs_mean is the FULL new
  * (N+1) x P matrix (mean::Data moves every row when a sample is added).  On an
  * empty handle D and P set the dimensions (gp.hpp:128-137); otherwise they
- * must match (gp.hpp:139-140 assert -> GPE_ERR_ARG). */
+ * must match (gp.hpp:139-140 assert -> GPE_ERR_ARG).  Returns 0, or n + 1 for n samples
+ * before the call when the new row's pivot is not positive (gpe_add_samples, gpe_append.h:
+ * n + t + 1 for the first such row t of the batch); the sample is appended either way. */
 int gpe_add_sample(gpe_handle h, const double* x, int D, const double* obs_mean, int P);
 /* gp.hpp:267-282 compute_log_lik */
 int gpe_log_lik(gpe_handle h, double* out);

@@ -202,7 +202,8 @@ void launch_lambda_rows(hipStream_t s, double* Xt, int64_t ld, int64_t col0, int
 // ---- Cholesky diagonal block (potrf.hip; the panel launches: potrf_panel.hip) --------------------------------------------
 // factor the jb x jb (jb <= 64) diagonal block at A (in place, lower) and write the transposed
 // inverse Xt[k + 64 c] = (L11^-1)[c][k] (64 x 64, identity-padded for jb < 64).  info: first bad
-// pivot (1-based, global index = goff + j + 1), written only if *info == 0.
+// pivot (1-based, global index = goff + j + 1): the word takes the minimum of what is reported
+// (diag_flow.h: report_pivot; the ragged block's round kernel, alone in its launch, writes if *info == 0).
 // half_form (jb == 64 only): only the inverses of the two 32 x 32 diagonal half-blocks are produced
 // (round 1; the data-flow block kernel of diag_flow.h leaves ALL of the inverse and ignores the flag).
 void launch_diag(hipStream_t s, double* A, int64_t lda, int jb, double* Xt, int* info, int64_t goff, int half_form);

@@ -497,6 +497,20 @@ static __device__ __forceinline__ void flow_x21(DiagSync* sy, const double* Xw, 
 }
 
 // ---- S ---------------------------------------------------------------------------------------------------------------------
+// The pivot word (pinned host memory; include/gpe.h: the 1-based index of the FIRST non-positive pivot) takes the MINIMUM of what
+// the diagonal blocks of a launch report: after a failed pivot every later block factors NaN and reports too, from another
+// workgroup — on another XCD, whose L2 neither sees an ordinary store of the first reporter nor gives its own up before the
+// launch ends.  "Read the word, write if zero" with ordinary accesses returned the index of a LATER block (N = 520, pivot 1: 193;
+// N = 704: 257).  System-scope accesses go past the L2s; the compare-and-swap makes the update a minimum whatever order the
+// reports arrive in.  Only a failing block comes here; a lost exchange means another reporter's value went in, so the loop ends
+// after at most as many rounds as there are reporters (bounded all the same).
+static __device__ __forceinline__ void report_pivot(int* info, int idx)
+{
+    int old = __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (int tries = 0; tries < 1024 && (old == 0 || old > idx); ++tries)
+        if (__hip_atomic_compare_exchange_strong(info, &old, idx, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM))
+            break;
+}
 template <int G>
 struct FlowS {
     static __device__ __forceinline__ void run(int& bad, const double* Ls, const double* invd,
@@ -584,6 +598,6 @@ static __device__ __forceinline__ void diag_flow(double* Ls, double* H, double* 
     }
     int bad = 0;
     FlowS<15>::run(bad, Ls, invd, Ad, lda, sy, lane, (ea && !ea->mute) ? ea->S + 1024 : nullptr);
-    if (lane == 0 && bad != 0 && *info == 0)
-        *info = (int)(goff + bad);
+    if (lane == 0 && bad != 0)
+        report_pivot(info, (int)(goff + bad));
 }

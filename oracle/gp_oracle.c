@@ -249,8 +249,13 @@ static int64_t potf2(double* A, int64_t nb, int64_t ld)
         double d = A_(A, j, j, ld);
         for (int64_t k = 0; k < j; ++k)
             d -= A_(A, j, k, ld) * A_(A, j, k, ld);
-        if (!(d > 0.0))
+        if (!(d > 0.0)) {
+            /* the pivot's own square root stays in L (NaN, or 0 for a zero pivot): whatever reads the factor afterwards —
+             * alpha, the log-likelihood — is not finite, for every position of the pivot (include/gpe.h, Conventions).
+             * Stopping with K's positive entry in place gave a finite number for a pivot in the leading columns. */
+            A_(A, j, j, ld) = sqrt(d);
             return j + 1;
+        }
         d = sqrt(d);
         A_(A, j, j, ld) = d;
         for (int64_t i = j + 1; i < nb; ++i) {
