@@ -56,6 +56,7 @@
 #include <limbo/model/gp/host_small.hpp>
 #include <limbo/model/gp/query_grad.hpp>
 #include <limbo/model/gp/pathwise.hpp>
+#include <limbo/model/gp/kg.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -66,6 +67,7 @@
 #include "../../../gpe_append.h"
 #include "../../../gpe_query_grad.h"
 #include "../../../gpe_batch_select.h"
+#include "../../../gpe_kg.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -494,6 +496,49 @@ namespace limbo {
                     score.resize((size_t)rc);
                 }
                 return rc;
+            }
+
+            /// Addition (include/gpe_kg.h, model/gp/kg.hpp): the knowledge gradient with correlated beliefs of every candidate over
+            /// a finite set of alternatives — the expected rise of the best posterior mean over the alternatives after ONE
+            /// observation of noise obs_noise at the candidate; with_self: the candidate counts among the alternatives.  mu_a / mu_c:
+            /// one COMPLETE mean per alternative / candidate (mean functor and aggregator applied by the caller), or empty:
+            /// k(X, v)^T alpha of output 0 with no mean functor (a constant mean moves nothing: the means enter as differences).
+            /// The model is not changed.  On the model's home device; no samples (the prior), a host-resident model below the
+            /// batch crossover and kernels without device code: on the host from the covariance of query_joint.
+            void knowledge_gradient(const std::vector<Eigen::VectorXd>& alternatives, const std::vector<Eigen::VectorXd>& candidates,
+                const std::vector<double>& mu_a, const std::vector<double>& mu_c, double obs_noise, bool with_self, std::vector<double>& kg) const
+            {
+                const int64_t A = alternatives.size(), M = candidates.size();
+                if (A < 1 || A > GPE_KG_MAX_ALTERNATIVES || !(obs_noise >= 0) || !std::isfinite(obs_noise)
+                    || (!mu_a.empty() && (int64_t)mu_a.size() != A) || (!mu_c.empty() && (int64_t)mu_c.size() != M))
+                    throw std::invalid_argument("limbo_amd: knowledge_gradient(): bad argument (include/gpe_kg.h)");
+                kg.assign((size_t)M, 0.0);
+                if (M == 0)
+                    return;
+                if (_joint_on_host(A + M)) {
+                    std::vector<Eigen::VectorXd> pts(alternatives);
+                    pts.insert(pts.end(), candidates.begin(), candidates.end());
+                    const int64_t T = A + M;
+                    std::vector<double> kta((size_t)(T * _dim_out)), cov((size_t)(T * T));
+                    _host_joint(pts, kta.data(), cov.data(), 0.0);
+                    if (!mu_a.empty())
+                        std::copy(mu_a.begin(), mu_a.end(), kta.begin());
+                    if (!mu_c.empty())
+                        std::copy(mu_c.begin(), mu_c.end(), kta.begin() + A);
+                    limbo_amd::kg_host::from_joint(cov.data(), kta.data(), A, M, obs_noise, with_self, kg.data());
+                }
+                else {
+                    const std::vector<double> Xa = _joint_points(alternatives), Xc = _joint_points(candidates);
+                    _eng.check(gpe_kg_batch(_eng.get(), Xa.data(), A, mu_a.empty() ? nullptr : mu_a.data(), Xc.data(), M,
+                                   mu_c.empty() ? nullptr : mu_c.data(), obs_noise, with_self ? 1 : 0, kg.data(), nullptr, nullptr, 0),
+                        "gpe_kg_batch");
+                }
+            }
+            /// ... with k(X, v)^T alpha of output 0 as the means and the kernel's noise as the observation's
+            void knowledge_gradient(const std::vector<Eigen::VectorXd>& alternatives, const std::vector<Eigen::VectorXd>& candidates, bool with_self,
+                std::vector<double>& kg) const
+            {
+                knowledge_gradient(alternatives, candidates, {}, {}, _kernel_function.noise(), with_self, kg);
             }
 
             /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise

@@ -21,6 +21,7 @@ ENGINE_SO = _PKG / "libgpengine.so"
 KERNEL_SE_ARD, KERNEL_MATERN52, KERNEL_MATERN32, KERNEL_EXP, KERNEL_HOST_K = range(5)
 KERNEL_NAMES = {"se_ard": 0, "matern52": 1, "matern32": 2, "exp": 3, "host_k": 4}
 SELECT_UCB, SELECT_EI, SELECT_VAR = range(3)  # include/gpe_batch_select.h: the rules of select_batch
+KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -148,6 +149,10 @@ def _sig(lib, prefix):
                              _dp, _i64],
             "select_phase_ms": [_vp, _dp],
             "debug_select_plan": [_i64, _i64, C.c_int, C.POINTER(_i64), _i64],
+            # include/gpe_kg.h: the knowledge gradient over a finite alternative set
+            "kg_batch": [_vp, _dp, _i64, _dp, _dp, _i64, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _i64],
+            "kg_envelope": [_vp, _dp, _i64, _dp, _i64, _i64, _dp, C.POINTER(C.c_int32)],
+            "kg_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -461,6 +466,51 @@ class Handle:
         ms = np.zeros(3)
         self._chk(self.lib.fn("select_phase_ms")(self._h, _d(ms)), "select_phase_ms")
         return dict(zip(("setup", "rounds", "readback"), ms.tolist()))
+
+    # -- the knowledge gradient over a finite alternative set (include/gpe_kg.h; HIP library only)
+    def kg_batch(self, Xa, Xc, obs_noise, with_self=False, mu_a=None, mu_c=None, want=("kg", "var", "cov"), check=True):
+        """The knowledge gradient of every row of Xc over the alternatives Xa.  mu_a / mu_c: complete means, or None for
+        k(X, .)^T alpha_0.  Returns (status, kg (M), var_c (M), cov (A, M)), None for what `want` leaves out.  check=False hands a
+        negative GPE_ERR_* back instead of raising."""
+        Xa = _c(Xa).reshape(-1, self.D)
+        Xc = _c(Xc).reshape(-1, self.D)
+        A, M = Xa.shape[0], Xc.shape[0]
+        ma = _c(np.asarray(mu_a, dtype=np.float64).reshape(A)) if mu_a is not None else None
+        mc = _c(np.asarray(mu_c, dtype=np.float64).reshape(M)) if mu_c is not None else None
+        kg = np.zeros(M) if "kg" in want else None
+        var = np.zeros(M) if "var" in want else None
+        cov = np.zeros((A, M), order="F") if "cov" in want else None
+        rc = self.lib.fn("kg_batch")(self._h, _d(Xa), A, _d(ma) if ma is not None else None, _d(Xc), M, _d(mc) if mc is not None else None,
+                                     float(obs_noise), int(bool(with_self)), _d(kg) if kg is not None else None,
+                                     _d(var) if var is not None else None, _d(cov) if cov is not None else None, max(A, 1))
+        if check:
+            self._chk(rc, "kg_batch")
+        return rc, kg, var, cov
+
+    def kg_envelope(self, a, B, ldb=None, want_nseg=True, check=True):
+        """h(a, B[:, m]) for every column of B (A x M, slopes already scaled) on host-supplied beliefs; any handle serves.  ldb:
+        hand B over with that leading dimension (>= A; a copy is made).  Returns (status, kg (M), nseg (M) or None)."""
+        a = _c(np.asarray(a, dtype=np.float64).reshape(-1))
+        B = np.asarray(B, dtype=np.float64)
+        B = B.reshape(B.shape[0], -1)
+        A, M = B.shape
+        assert a.shape[0] == A
+        ld = A if ldb is None else int(ldb)
+        Bf = np.zeros((max(ld, A), M), order="F")
+        Bf[:A] = B
+        kg = np.zeros(M)
+        nseg = np.zeros(M, dtype=np.int32) if want_nseg else None
+        rc = self.lib.fn("kg_envelope")(self._h, _d(a), A, _d(Bf), ld, M, _d(kg),
+                                        nseg.ctypes.data_as(C.POINTER(C.c_int32)) if want_nseg else None)
+        if check:
+            self._chk(rc, "kg_envelope")
+        return rc, kg, nseg
+
+    def kg_phase_ms(self):
+        """{alternatives, candidates, envelope, readback} of the last kg_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(4)
+        self._chk(self.lib.fn("kg_phase_ms")(self._h, _d(ms)), "kg_phase_ms")
+        return dict(zip(("alternatives", "candidates", "envelope", "readback"), ms.tolist()))
 
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)
     def query_batch_grad(self, Xq, want=("kta", "var", "dkta", "dvar")):

@@ -539,6 +539,14 @@ void launch_sel_transpose(hipStream_t s, const double* Z, int64_t ld, int64_t N,
 void launch_sel_score0(hipStream_t s, const SelRound& g);      // the scores of round 0 and its pick
 void launch_sel_round(hipStream_t s, const SelRound& g, int t); // round t: gather, column product, fold, the pick of round t + 1
 
+// ---- the knowledge gradient over a finite alternative set (kg.hip; include/gpe_kg.h) --------------------------------------
+// kg[m] = h(a, b_m) for m < M, one workgroup each.  var == null: column m of B (A x M, ldb) holds the slopes.  Otherwise B is the
+// unscaled covariance and b = B[:, m] / sqrt(var[m] + obs_noise) — kg[m] = 0 where that sum is not above DBL_EPSILON or not
+// finite — and, with_self, the candidate itself is line A: (mu_c[m], var[m] / sqrt(var[m] + obs_noise)).  nseg (may be null): the
+// steps of the chain.  A <= GPE_KG_MAX_ALTERNATIVES (the lines, their breakpoints and successors are in LDS).
+void launch_kg_envelope(hipStream_t s, const double* a, int A, const double* B, int64_t ldb, int64_t M, const double* var, double obs_noise,
+                        int with_self, const double* mu_c, double* kg, int* nseg);
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);

@@ -1,0 +1,183 @@
+// kg.hpp — the knowledge gradient over a finite alternative set (include/gpe_kg.h): host side.  Kernel: kg.hip.
+// A part of engine.hip's translation unit (included there, once, behind query.hpp, joint.hpp and select.hpp, whose helpers it shares).
+#pragma once
+
+// Candidates per chunk of the N x M layout (fewer samples than one outer panel): the blocked solve picks its tile from the
+// column count above some ten thousand columns, and a candidate's answer must not depend on the batch around it
+static const int64_t kKgNmChunk = 8192;
+
+// Called with the handle's mutex held; A in [1, GPE_KG_MAX_ALTERNATIVES], M > 0, arguments checked.
+static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, const double* Xc, int64_t M, const double* mu_c,
+                   double obs_noise, int with_self, double* kg, double* var_c, double* cov, int64_t ldc)
+{
+    hipStream_t s = c->stream;
+    digest_kernel(c);
+    const int64_t N = c->N;
+    const int D = c->D;
+    const bool transposed = qt_serves(c);
+    // two sets of chunk buffers in one lease of the scratch: the alternatives' (resident for the call: Zt_a, a) and a candidate chunk's
+    const int64_t ma_max = round_up(A, 64);
+    const int64_t mc_max = transposed ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk);
+    QtBufs ba = transposed ? qt_layout(c, ma_max, N) : nm_layout(c, ma_max, false);
+    QtBufs bc = transposed ? qt_layout(c, mc_max, N) : nm_layout(c, mc_max, false);
+    const int64_t ldx = ma_max + 16; // the cross-covariance: A x mc, column-major, alternatives contiguous (even: 16-byte columns)
+    const size_t n_a = (size_t)ma_max, n_c = (size_t)(ldx * mc_max), n_kg = (size_t)mc_max, n_mu = (size_t)mc_max;
+    QueryScratch qs(c);
+    if (const int e = qs.carve(ba, bc.doubles + n_a + n_c + n_kg + n_mu))
+        return e;
+    qt_carve(bc, ba.dKvv + ba.mc_max);
+    double* dA = bc.dKvv + bc.mc_max;
+    double* dC = dA + n_a;
+    double* dKg = dC + n_c;
+    double* dMu = dKg + n_kg;
+
+    Marks mk(c->pool, s, c->prof);
+    double ms[4] = {0, 0, 0, 0};
+    // the alternatives, once: Zt_a (transposed: ba.dZt, ba.ldq; else Z_a = L^-1 k(X, Xa) in ba.dKst, the samples contiguous) and a
+    const int t0 = mk.mark();
+    if (transposed) {
+        qt_panels(c, ba);
+        qt_chunk(c, ba, Xa, A, mu_a == nullptr, nullptr, 0, A, true);
+    }
+    else {
+        chunk_head(c, ba, Xa, true, A, true, mu_a == nullptr, nullptr, 0, A);
+        trsm_left_blocked(c, c->dA, ba.dKst, c->ld, N, A, false, GPE_PH_QUERY); // gp.hpp:620
+    }
+    if (mu_a)
+        HIPCHK(c, hipMemcpyAsync(dA, mu_a, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, s));
+    const double* da = mu_a ? dA : ba.dKta; // (output 0: the first column of kta)
+    const int t1 = mk.mark();
+    int rc = GPE_OK;
+    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
+        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
+        const bool want_kta = with_self && !mu_c;
+        const int u0 = mk.mark();
+        // the chunk's head and solve as a query's, then s
+        if (transposed) {
+            chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
+            qt_forward(c, bc, mc, c, ba.dXp, bc.dKst, bc.dZt);
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
+            launch_kvv(s, bc.dQt, bc.ldq, mc, c->kp, bc.dKvv);
+            launch_row_var_t(s, bc.dZt, bc.ldq, N, mc, bc.dKvv, bc.dVar, bc.dPart, bc.ldq, bc.nseg); // gp.hpp:621
+        }
+        else {
+            chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
+            trsm_left_blocked(c, c->dA, bc.dKst, c->ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
+            launch_kvv(s, bc.dQt, bc.ldq, mc, c->kp, bc.dKvv);
+            launch_col_var(s, bc.dKst, c->ld, N, mc, bc.dKvv, bc.dVar); // gp.hpp:621
+        }
+        {
+            // c = k(Xa, Xc) - Zt_a Zt_c^T on the matrix cores: the tile from N alone, the k range whole (no split: nothing of
+            // the product depends on M or on where in the batch a candidate stands)
+            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * (double)A * mc * N);
+            launch_build_Ks(s, ba.dQt, ba.ldq, A, bc.dQt, bc.ldq, mc, c->kp, dC, ldx);
+            GemmArgs g{};
+            g.C = dC;
+            g.ldc = ldx;
+            g.A = transposed ? ba.dZt : ba.dKst;
+            g.lda = transposed ? ba.ldq : c->ld;
+            g.B = transposed ? bc.dZt : bc.dKst;
+            g.ldb = transposed ? bc.ldq : c->ld;
+            g.a_kmajor = g.b_kmajor = transposed ? 0 : 1;
+            g.m = A;
+            g.n = mc;
+            g.k = N;
+            g.tile = qt_tile(N);
+            launch_gemm_sub(s, g);
+        }
+        if (with_self && mu_c)
+            HIPCHK(c, hipMemcpyAsync(dMu, mu_c + m0, sizeof(double) * (size_t)mc, hipMemcpyHostToDevice, s));
+        const int u1 = mk.mark();
+        if (kg) {
+            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
+            launch_kg_envelope(s, da, (int)A, dC, ldx, mc, bc.dVar, obs_noise, with_self, mu_c ? dMu : bc.dKta, dKg, nullptr);
+        }
+        const int u2 = mk.mark();
+        if (kg)
+            HIPCHK(c, hipMemcpyAsync(kg + m0, dKg, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+        if (var_c)
+            HIPCHK(c, hipMemcpyAsync(var_c + m0, bc.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+        if (cov)
+            HIPCHK(c, copy2d_to_host(cov + m0 * ldc, ldc, dC, ldx, A, mc, s));
+        const int u3 = mk.mark();
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            c->err = "kg_batch: stream sync failed";
+            rc = GPE_ERR_HIP;
+        }
+        ms[1] += mk.ms(u0, u1);
+        ms[2] += mk.ms(u1, u2);
+        ms[3] += mk.ms(u2, u3);
+    }
+    if (c->prof && rc == GPE_OK) {
+        ms[0] = mk.ms(t0, t1);
+        for (int q = 0; q < 4; ++q)
+            c->kg_ms[q] = ms[q];
+    }
+    drain_phases(c);
+    return rc;
+}
+
+int gpe_kg_batch(gpe_handle c, const double* Xa, int64_t A, const double* mu_a, const double* Xc, int64_t M, const double* mu_c,
+                 double obs_noise, int with_self, double* kg, double* var_c, double* cov, int64_t ldc)
+{
+    if (!c || A < 1 || A > GPE_KG_MAX_ALTERNATIVES || M < 0 || !(obs_noise >= 0.0) || !std::isfinite(obs_noise) || !Xa || (M > 0 && !Xc)
+        || (cov && ldc < A))
+        return GPE_ERR_ARG;
+    if (!c->have_L)
+        return GPE_ERR_STATE;
+    if (c->host_K)
+        return GPE_ERR_UNSUPPORTED;
+    if (M == 0 || (!kg && !var_c && !cov))
+        return GPE_OK;
+    DevGuard g(c);
+    std::lock_guard<std::mutex> lk(c->mu);
+    return kg_impl(c, Xa, A, mu_a, Xc, M, mu_c, obs_noise, with_self ? 1 : 0, kg, var_c, cov, ldc);
+}
+
+// The envelope alone, on host-supplied beliefs: any handle, computed or not (its device, stream and scratch are all it takes)
+int gpe_kg_envelope(gpe_handle c, const double* a, int64_t A, const double* B, int64_t ldb, int64_t M, double* kg, int32_t* nseg)
+{
+    if (!c || A < 1 || A > GPE_KG_MAX_ALTERNATIVES || M < 0 || ldb < A || !a || (M > 0 && (!B || !kg)))
+        return GPE_ERR_ARG;
+    if (c->host_K)
+        return GPE_ERR_UNSUPPORTED;
+    if (M == 0)
+        return GPE_OK;
+    DevGuard g(c);
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t s = c->stream;
+    const int64_t mc_max = std::min<int64_t>(M, 16384); // columns on the device at once
+    const size_t n_a = (size_t)round_up(A, 2), n_b = (size_t)(A * mc_max), n_kg = (size_t)mc_max, n_seg = (size_t)(mc_max + 1) / 2;
+    QueryScratch qs(c);
+    if (const int e = qs.reserve(n_a + n_b + n_kg + n_seg))
+        return e;
+    double* dA = c->dQuery;
+    double* dB = dA + n_a;
+    double* dKg = dB + n_b;
+    int* dSeg = (int*)(dKg + n_kg);
+    HIPCHK(c, hipMemcpyAsync(dA, a, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, s));
+    for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
+        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
+        HIPCHK(c, copy2d_from_host(dB, A, B + m0 * ldb, ldb, A, mc, s));
+        launch_kg_envelope(s, dA, (int)A, dB, A, mc, nullptr, 0.0, 0, nullptr, dKg, dSeg);
+        HIPCHK(c, hipMemcpyAsync(kg + m0, dKg, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+        if (nseg)
+            HIPCHK(c, hipMemcpyAsync(nseg + m0, dSeg, sizeof(int) * (size_t)mc, hipMemcpyDeviceToHost, s));
+        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
+            c->err = "kg_envelope: stream sync failed";
+            return GPE_ERR_HIP;
+        }
+    }
+    return GPE_OK;
+}
+
+int gpe_kg_phase_ms(gpe_handle c, double* ms4)
+{
+    if (!c || !ms4)
+        return GPE_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    for (int q = 0; q < 4; ++q)
+        ms4[q] = c->kg_ms[q];
+    return GPE_OK;
+}
