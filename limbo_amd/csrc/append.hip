@@ -1,6 +1,6 @@
 // append.hip — the device tail of a blocked append (include/gpe_append.h): q <= AP_CHUNK new samples V join a factor of order n.
 //
-//   Zt[a + k ldq] = (L^-1 k(X, v_a))_k            the transposed layout of query.hpp, left by qt_chunk
+//   Zt[a + k ldq] = (L^-1 k(X, v_a))_k            the transposed layout of query.hpp, left by chunk_solve
 //   S  = k(V, V) + diag_add I - Zt Zt^T           gp.hpp:583-597 for a block; C = chol(S), lower
 //   L[n + a, k] = Zt[a, k]  (k < n),   L[n + a, n + b] = C[a, b]
 //

@@ -4,8 +4,8 @@
 #pragma once
 
 // The launch list of one chunk of mc <= append_max_chunk() points on a factor of order n ("Blocked append"):
-//   qt_panels                 1   inverses of the 256-column diagonal panels (inv.hip)
-//   qt_chunk(want_z)          3 + 2 ceil(n / 256) - 1: points to SoA (+ Lambda rows), cross kernel, then per panel the product
+//   chunk_begin               1   inverses of the 256-column diagonal panels (inv.hip)
+//   chunk_head, chunk_solve   3 + 2 ceil(n / 256) - 1: points to SoA (+ Lambda rows), cross kernel, then per panel the product
 //                             with the panel inverse and the update of what lies right of it — Zt = Kst L^-T on the matrix cores
 //   copy2d                    1   the points' SoA columns n .. n + mc - 1 of Xt (they are SoA already: no second transposition)
 //   launch_append_tail        3   partial products + rows of L | fold + k(V, V) | factorisation + C + pivot word (append.hip)
@@ -13,6 +13,12 @@
 // and once per call, behind the last chunk: solve_alpha (two sweeps), the log-likelihood terms, compute_finish (the one host wait).
 // (extra: the tail's scratch in front of the chunk buffers in dQuery, slices_cap partial matrices and S — sized by the caller for
 // the largest order the call reaches, append_scratch_doubles(nb0 + rem))
+// The call's scratch: the tail's, then a chunk's buffers — reserved once for the last chunk's layout, placed per chunk for its own
+static void append_regions(Carver& cv, size_t extra, QtBufs& b)
+{
+    cv.take<double>(extra);
+    qt_carve(b, cv);
+}
 static int append_enqueue(gpe_ctx* c, const double* Xb, int64_t nb0, int64_t rem, size_t extra, int slices_cap)
 {
     hipStream_t s = c->stream;
@@ -21,9 +27,11 @@ static int append_enqueue(gpe_ctx* c, const double* Xb, int64_t nb0, int64_t rem
     for (int64_t m0 = 0; m0 < rem; m0 += CH) {
         const int64_t mc = std::min<int64_t>(CH, rem - m0), n = c->N;
         QtBufs b = qt_layout(c, CH, n); // (the chunk in front of this one is part of L by now)
-        qt_carve(b, c->dQuery + extra);
-        qt_panels(c, b);
-        qt_chunk(c, b, Xb + m0 * c->D, mc, false, nullptr, 0, 0, true);
+        Carver cv(c->dQuery.get());
+        append_regions(cv, extra, b);
+        chunk_begin(c, b, true);
+        chunk_head(c, b, Xb + m0 * c->D, true, mc, true, false, nullptr, 0, 0);
+        chunk_solve(c, b, mc);
         {
             PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)mc * mc * n + (double)mc * mc * mc / 3.0);
             launch_copy2d(s, b.dQt, b.ldq, c->dXt + n, ld, mc, c->kp.D);
@@ -128,8 +136,9 @@ int gpe_add_samples(gpe_handle c, const double* X, int64_t q, int D, const doubl
     // 65 536 samples: append_slices_cap) and the chunk buffers of the last chunk's layout, which grows with n
     const int slices_cap = append_slices_cap(nfin);
     const size_t extra = append_scratch_doubles(nfin);
+    QtBufs blast = qt_layout(c, append_max_chunk(), nfin, nfin);
     QueryScratch qs(c);
-    if (const int e = qs.reserve(extra + qt_layout(c, append_max_chunk(), nfin, nfin).doubles))
+    if (const int e = qs.carve([&](Carver& cv) { append_regions(cv, extra, blast); }))
         return e;
     HIPCHK(c, copy2d_from_host(c->dOm, c->ld, obs_mean, nfin, nfin, P, s));
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here

@@ -25,6 +25,7 @@
 #include "../../include/gpe_kg.h"
 #include "dev.h"
 #include "devbuf.h"
+#include "carve.h" // (the typed scratch carver of query.hpp: a template, so outside the extern "C" block below)
 
 #include <algorithm>
 #include <cmath>

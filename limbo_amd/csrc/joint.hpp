@@ -2,7 +2,7 @@
 // A part of engine.hip's translation unit (included there, once, behind query.hpp, whose chunk helpers it shares).
 #pragma once
 
-// M above this is GPE_ERR_ARG: all M rows of Zt are resident at once (one chunk of query_transposed), and Sigma, its factor and
+// M above this is GPE_ERR_ARG: all M rows of Zt are resident at once (one chunk of the batched query), and Sigma, its factor and
 // the partial matrices of the split are M x M each
 static int64_t joint_max_points(const gpe_ctx* c)
 {
@@ -91,9 +91,7 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     digest_kernel(c);
     const int64_t N = c->N;
     const int P = c->P;
-    // Fewer samples than one outer panel: the N x M layout of
-    // query_impl — Z = L^-1 Ks by the blocked solve, k-contiguous operands — and the composed covariance path only
-    const bool transposed = qt_serves(c); // (GPE_QUERY_T is not asked here)
+    PhaseDrain pd(c);
     const bool want_cov = cov != nullptr || dr != nullptr;
     gpe_ctx* sc = nullptr;
     if (want_cov) {
@@ -105,43 +103,41 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
     // the split's k range runs to N rounded up to the k step over zero columns of Zt
     const int64_t N16 = round_up(N, 16);
-    const bool splitk = transposed && joint_use_splitk(M, cus);
-    const int nch = want_cov && splitk ? joint_cov_chunks(M, N, cus) : 0;
     const int64_t mc_max = round_up(M, 64);
-    QtBufs b = transposed ? qt_layout(c, mc_max, N16) : nm_layout(c, mc_max, false);
+    QtBufs b = served_layout(c, mc_max, N16); // (GPE_QUERY_T is not asked here)
+    // the split reads Zt tile by tile, the points contiguous: with fewer samples than one outer panel (the N x M layout: Z by the
+    // blocked solve, the samples contiguous) the composed covariance path only
+    const bool splitk = b.transposed && joint_use_splitk(M, cus);
+    const int nch = want_cov && splitk ? joint_cov_chunks(M, N, cus) : 0;
     const int ncols = dr ? dr->S * P : 0;
     const int64_t nt = (M + 127) / 128, nitems = nt * (nt + 1) / 2 * std::max(nch, 0);
-    const size_t n_part = (size_t)nch * (size_t)(b.ldq * M);              // the partial matrices, ldq x M each
-    const size_t n_items = (sizeof(GemmItem) * (size_t)nitems + 7) / 8;   // (in doubles)
-    const size_t n_bins = (sizeof(int32_t) * (size_t)(nitems + 1) + 7) / 8;
     const size_t n_z = (size_t)M * ncols, n_mq = dr && dr->mean_q ? (size_t)M * P : 0, n_am = 2 * (size_t)ncols;
+    double *dPartM = nullptr, *dZn = nullptr, *dF = nullptr, *dMq = nullptr, *dAm = nullptr;
+    GemmItem* dItems = nullptr;
+    int32_t* dBins = nullptr;
     QueryScratch qs(c);
-    if (const int e = qs.carve(b, n_part + n_items + n_bins + 2 * n_z + n_mq + n_am))
+    if (const int e = qs.carve([&](Carver& cv) {
+            qt_carve(b, cv);
+            dPartM = cv.take<double>((size_t)nch * (size_t)(b.ldq * M)); // the partial matrices, ldq x M each
+            dItems = cv.take<GemmItem>((size_t)nitems);
+            dBins = cv.take<int32_t>((size_t)nitems + 1);
+            dZn = cv.take<double>(n_z);
+            dF = cv.take<double>(n_z);
+            dMq = cv.take<double>(n_mq);
+            dAm = cv.take<double>(n_am);
+        }))
         return e;
-    double* dPartM = b.dKvv + b.mc_max;
-    GemmItem* dItems = (GemmItem*)(dPartM + n_part);
-    int32_t* dBins = (int32_t*)((double*)dItems + n_items);
-    double* dZn = (double*)dBins + n_bins;
-    double* dF = dZn + n_z;
-    double* dMq = dF + n_z;
-    double* dAm = dMq + n_mq;
 
     // (profiling: the call's own phases — Z, Sigma, the factorisation, the draws — for gpe_joint_phase_ms)
     Marks mk(c->pool, s, c->prof);
     const int t0 = mk.mark();
-    if (!transposed) {
-        chunk_head(c, b, Xq, true, M, true, kta != nullptr || dr != nullptr, kta, 0, M);
-        if (want_cov)
-            trsm_left_blocked(c, c->dA, b.dKst, c->ld, N, M, false, GPE_PH_QUERY); // gp.hpp:620
-    }
-    else {
-        if (want_cov) {
-            qt_panels(c, b);
-            if (N16 > N)
-                HIPCHK(c, hipMemsetAsync(b.dZt + N * b.ldq, 0, sizeof(double) * (size_t)((N16 - N) * b.ldq), s));
-        }
-        qt_chunk(c, b, Xq, M, kta != nullptr || dr != nullptr, kta, 0, M, want_cov);
-    }
+    chunk_begin(c, b, want_cov);
+    if (want_cov && b.n_zt > (size_t)(N * b.ldq)) // (the zero columns behind Zt's N)
+        HIPCHK(c, hipMemsetAsync(b.dZt + N * b.ldq, 0, sizeof(double) * (b.n_zt - (size_t)(N * b.ldq)), s));
+    chunk_head(c, b, Xq, true, M, true, kta != nullptr || dr != nullptr, kta, 0, M);
+    ZView z;
+    if (want_cov)
+        z = chunk_solve(c, b, M); // gp.hpp:620
     const int t1 = mk.mark();
     std::vector<GemmItem> items; // (host copies of the launch list: alive until the stream has been waited for, below)
     std::vector<int32_t> bins;
@@ -181,9 +177,7 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         GemmArgs g{};
         g.C = sc->dKhost;
         g.ldc = sc->ld;
-        g.A = g.B = transposed ? b.dZt : b.dKst;
-        g.lda = g.ldb = transposed ? b.ldq : c->ld;
-        g.a_kmajor = g.b_kmajor = transposed ? 0 : 1;
+        z_operands(g, z, z);
         g.m = M;
         g.n = M;
         g.k = N;
@@ -201,11 +195,8 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         if (n_mq)
             HIPCHK(c, hipMemcpyAsync(dMq, dr->mean_q, sizeof(double) * n_mq, hipMemcpyHostToDevice, s));
     }
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        c->err = "joint posterior: stream sync failed";
-        drain_phases(c);
-        return GPE_ERR_HIP;
-    }
+    if (const int e = stream_wait(c, "joint posterior", true))
+        return e;
     int rc = GPE_OK;
     if (dr) {
         // C = chol(Sigma + jitter I) by the engine's factorisation schedule, in the scratch context (Sigma is complete: the
@@ -234,11 +225,8 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
                 HIPCHK(c, hipMemcpyAsync(dr->F, dF, sizeof(double) * n_z, hipMemcpyDeviceToHost, s));
             if (dr->argmax || dr->fmax)
                 HIPCHK(c, hipMemcpyAsync(am.data(), dAm, sizeof(double) * n_am, hipMemcpyDeviceToHost, s));
-            if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-                c->err = "joint posterior: stream sync failed";
-                rc = GPE_ERR_HIP;
-            }
-            else
+            rc = stream_wait(c, "joint posterior", true);
+            if (rc == GPE_OK)
                 for (int q = 0; q < ncols; ++q) {
                     if (dr->fmax)
                         dr->fmax[q] = am[2 * (size_t)q];
@@ -254,7 +242,6 @@ static int joint_impl(gpe_ctx* c, const double* Xq, int64_t M, double jitter, do
         if (!dr)
             c->joint_ms[2] = 0.0;
     }
-    drain_phases(c);
     return rc;
 }
 

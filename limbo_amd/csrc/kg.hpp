@@ -14,35 +14,32 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
     digest_kernel(c);
     const int64_t N = c->N;
     const int D = c->D;
-    const bool transposed = qt_serves(c);
-    // two sets of chunk buffers in one lease of the scratch: the alternatives' (resident for the call: Zt_a, a) and a candidate chunk's
+    PhaseDrain pd(c);
+    // two sets of chunk buffers in one lease of the scratch: the alternatives' (resident for the call: Z_a, a) and a candidate chunk's
     const int64_t ma_max = round_up(A, 64);
-    const int64_t mc_max = transposed ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk);
-    QtBufs ba = transposed ? qt_layout(c, ma_max, N) : nm_layout(c, ma_max, false);
-    QtBufs bc = transposed ? qt_layout(c, mc_max, N) : nm_layout(c, mc_max, false);
+    const int64_t mc_max = qt_serves(c) ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk);
+    QtBufs ba = served_layout(c, ma_max, N), bc = served_layout(c, mc_max, N);
     const int64_t ldx = ma_max + 16; // the cross-covariance: A x mc, column-major, alternatives contiguous (even: 16-byte columns)
-    const size_t n_a = (size_t)ma_max, n_c = (size_t)(ldx * mc_max), n_kg = (size_t)mc_max, n_mu = (size_t)mc_max;
+    double *dA = nullptr, *dC = nullptr, *dKg = nullptr, *dMu = nullptr;
     QueryScratch qs(c);
-    if (const int e = qs.carve(ba, bc.doubles + n_a + n_c + n_kg + n_mu))
+    if (const int e = qs.carve([&](Carver& cv) {
+            qt_carve(ba, cv);
+            qt_carve(bc, cv);
+            dA = cv.take<double>((size_t)ma_max);
+            dC = cv.take<double>((size_t)(ldx * mc_max));
+            dKg = cv.take<double>((size_t)mc_max);
+            dMu = cv.take<double>((size_t)mc_max);
+        }))
         return e;
-    qt_carve(bc, ba.dKvv + ba.mc_max);
-    double* dA = bc.dKvv + bc.mc_max;
-    double* dC = dA + n_a;
-    double* dKg = dC + n_c;
-    double* dMu = dKg + n_kg;
+    bc.dXp = ba.dXp; // (the panel inverses are the model's: one set serves both)
 
     Marks mk(c->pool, s, c->prof);
     double ms[4] = {0, 0, 0, 0};
-    // the alternatives, once: Zt_a (transposed: ba.dZt, ba.ldq; else Z_a = L^-1 k(X, Xa) in ba.dKst, the samples contiguous) and a
+    // the alternatives, once: Z_a = L^-1 k(X, Xa) and a
     const int t0 = mk.mark();
-    if (transposed) {
-        qt_panels(c, ba);
-        qt_chunk(c, ba, Xa, A, mu_a == nullptr, nullptr, 0, A, true);
-    }
-    else {
-        chunk_head(c, ba, Xa, true, A, true, mu_a == nullptr, nullptr, 0, A);
-        trsm_left_blocked(c, c->dA, ba.dKst, c->ld, N, A, false, GPE_PH_QUERY); // gp.hpp:620
-    }
+    chunk_begin(c, ba, true);
+    chunk_head(c, ba, Xa, true, A, true, mu_a == nullptr, nullptr, 0, A);
+    const ZView za = chunk_solve(c, ba, A);
     if (mu_a)
         HIPCHK(c, hipMemcpyAsync(dA, mu_a, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, s));
     const double* da = mu_a ? dA : ba.dKta; // (output 0: the first column of kta)
@@ -52,34 +49,19 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
         const bool want_kta = with_self && !mu_c;
         const int u0 = mk.mark();
-        // the chunk's head and solve as a query's, then s
-        if (transposed) {
-            chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
-            qt_forward(c, bc, mc, c, ba.dXp, bc.dKst, bc.dZt);
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, bc.dQt, bc.ldq, mc, c->kp, bc.dKvv);
-            launch_row_var_t(s, bc.dZt, bc.ldq, N, mc, bc.dKvv, bc.dVar, bc.dPart, bc.ldq, bc.nseg); // gp.hpp:621
-        }
-        else {
-            chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
-            trsm_left_blocked(c, c->dA, bc.dKst, c->ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, bc.dQt, bc.ldq, mc, c->kp, bc.dKvv);
-            launch_col_var(s, bc.dKst, c->ld, N, mc, bc.dKvv, bc.dVar); // gp.hpp:621
-        }
+        // the chunk's head, solve and variance as a query's
+        chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
+        const ZView zc = chunk_solve(c, bc, mc);
+        chunk_var(c, bc, mc, zc);
         {
-            // c = k(Xa, Xc) - Zt_a Zt_c^T on the matrix cores: the tile from N alone, the k range whole (no split: nothing of
+            // c = k(Xa, Xc) - Z_a^T Z_c on the matrix cores: the tile from N alone, the k range whole (no split: nothing of
             // the product depends on M or on where in the batch a candidate stands)
             PhaseScope ps(c, GPE_PH_QUERY, 2.0 * (double)A * mc * N);
             launch_build_Ks(s, ba.dQt, ba.ldq, A, bc.dQt, bc.ldq, mc, c->kp, dC, ldx);
             GemmArgs g{};
             g.C = dC;
             g.ldc = ldx;
-            g.A = transposed ? ba.dZt : ba.dKst;
-            g.lda = transposed ? ba.ldq : c->ld;
-            g.B = transposed ? bc.dZt : bc.dKst;
-            g.ldb = transposed ? bc.ldq : c->ld;
-            g.a_kmajor = g.b_kmajor = transposed ? 0 : 1;
+            z_operands(g, za, zc);
             g.m = A;
             g.n = mc;
             g.k = N;
@@ -101,10 +83,7 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
         if (cov)
             HIPCHK(c, copy2d_to_host(cov + m0 * ldc, ldc, dC, ldx, A, mc, s));
         const int u3 = mk.mark();
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            c->err = "kg_batch: stream sync failed";
-            rc = GPE_ERR_HIP;
-        }
+        rc = stream_wait(c, "kg_batch", true);
         ms[1] += mk.ms(u0, u1);
         ms[2] += mk.ms(u1, u2);
         ms[3] += mk.ms(u2, u3);
@@ -114,7 +93,6 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
         for (int q = 0; q < 4; ++q)
             c->kg_ms[q] = ms[q];
     }
-    drain_phases(c);
     return rc;
 }
 
@@ -148,14 +126,16 @@ int gpe_kg_envelope(gpe_handle c, const double* a, int64_t A, const double* B, i
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t s = c->stream;
     const int64_t mc_max = std::min<int64_t>(M, 16384); // columns on the device at once
-    const size_t n_a = (size_t)round_up(A, 2), n_b = (size_t)(A * mc_max), n_kg = (size_t)mc_max, n_seg = (size_t)(mc_max + 1) / 2;
+    double *dA = nullptr, *dB = nullptr, *dKg = nullptr;
+    int* dSeg = nullptr;
     QueryScratch qs(c);
-    if (const int e = qs.reserve(n_a + n_b + n_kg + n_seg))
+    if (const int e = qs.carve([&](Carver& cv) {
+            dA = cv.take<double>((size_t)A);
+            dB = cv.take<double>((size_t)(A * mc_max));
+            dKg = cv.take<double>((size_t)mc_max);
+            dSeg = cv.take<int>((size_t)mc_max);
+        }))
         return e;
-    double* dA = c->dQuery;
-    double* dB = dA + n_a;
-    double* dKg = dB + n_b;
-    int* dSeg = (int*)(dKg + n_kg);
     HIPCHK(c, hipMemcpyAsync(dA, a, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, s));
     for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
@@ -164,10 +144,8 @@ int gpe_kg_envelope(gpe_handle c, const double* a, int64_t A, const double* B, i
         HIPCHK(c, hipMemcpyAsync(kg + m0, dKg, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
         if (nseg)
             HIPCHK(c, hipMemcpyAsync(nseg + m0, dSeg, sizeof(int) * (size_t)mc, hipMemcpyDeviceToHost, s));
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            c->err = "kg_envelope: stream sync failed";
-            return GPE_ERR_HIP;
-        }
+        if (const int e = stream_wait(c, "kg_envelope", true))
+            return e;
     }
     return GPE_OK;
 }

@@ -80,10 +80,8 @@ static int paths_columns(gpe_ctx* c, gpe_paths_ctx* ps, const double* E, int c0,
     const double* dWt = solve();
     launch_paths_untranspose(s, dWt, ldt, N, nc, ps->dU + (int64_t)c0 * ps->ldx, ps->ldx);
     mk.mark();
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        c->err = "paths_create: stream sync failed";
-        return GPE_ERR_HIP;
-    }
+    if (const int e = stream_wait(c, "paths_create", true))
+        return e;
     for (int q = 0; q < 2; ++q)
         ps->ms[q] += mk.ms(q, q + 1);
     return GPE_OK;
@@ -113,7 +111,7 @@ static int paths_solve_transposed(gpe_ctx* c, gpe_paths_ctx* ps, const double* E
     return rc;
 }
 
-// Where the transposed layout does not serve the model: Wt = Rt K^-1 in one product (K^-1: ensure_inv, as qgrad_by_inverse)
+// Where the transposed layout does not serve the model: Wt = Rt K^-1 in one product (K^-1: ensure_inv, as qgrad_impl)
 static int paths_solve_by_inverse(gpe_ctx* c, gpe_paths_ctx* ps, const double* E)
 {
     const int64_t N = c->N, ld = c->ld;

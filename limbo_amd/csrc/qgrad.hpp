@@ -84,116 +84,78 @@ static void qt_backward(gpe_ctx* c, const QtBufs& b, int64_t mc)
     }
 }
 
-// The transposed layout (query_transposed's loop): Zt = Kst L^-T, var from Zt, then Wt = Zt L^-1 into the buffer Kst occupied.
-static int qgrad_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
-{
-    hipStream_t s = c->stream;
-    const int64_t N = c->N;
-    const int D = c->D;
-    const int64_t mc_max = qt_rows_per_chunk(N, M);
-    QtBufs b = qt_layout(c, mc_max, N);
-    size_t n_partg = 0, n_g = 0;
-    const bool grads = dkta || dvar, want_z = var || dvar;
-    if (grads)
-        qg_extra(c, b.nseg, b.ldq, mc_max, &n_partg, &n_g);
-    QueryScratch qs(c);
-    if (const int e = qs.carve(b, n_partg + n_g))
-        return e;
-    double* dPartG = b.dKvv + b.mc_max;
-    double* dG = dPartG + n_partg;
-    int rc = GPE_OK;
-    if (want_z)
-        qt_panels(c, b);
-    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
-        const int64_t mc = std::min<int64_t>(mc_max, M - m0), ldq = b.ldq;
-        Marks mk(c->pool, s, c->prof);
-        mk.mark();
-        qt_chunk(c, b, Xq + m0 * D, mc, kta != nullptr, kta, m0, M, want_z);
-        if (var) { // (before Zt is consumed below)
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, b.dQt, ldq, mc, c->kp, b.dKvv);
-            launch_row_var_t(s, b.dZt, ldq, N, mc, b.dKvv, b.dVar, b.dPart, ldq, b.nseg); // gp.hpp:621
-            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
-        }
-        mk.mark();
-        if (dvar)
-            qt_backward(c, b, mc);
-        mk.mark();
-        if (grads)
-            qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? b.dKst : nullptr, ldq, b.nseg, dPartG, dG, dkta, dvar, m0, M);
-        mk.mark();
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            c->err = "query_batch_grad: stream sync failed";
-            rc = GPE_ERR_HIP;
-        }
-        qg_collect(c, mk);
-    }
-    drain_phases(c);
-    return rc;
-}
-
-// Where the transposed layout does not serve the model: kta and var by the launches of query_impl's blocked N x M path, and
-// Wt = Kst K^-1 in one product (K^-1: ensure_inv, cached on the handle until K changes; a symmetric copy of its lower triangle)
-static int qgrad_by_inverse(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
+// kta and var by the chunk steps of the batched query, then Wt = Kst K^-1 (mc x N, the points contiguous) for the variance's gradient:
+//   transposed layout: Wt = Zt L^-1 (qt_backward) into the buffer Kst occupied;
+//   else: one product with K^-1 (ensure_inv, cached on the handle until K changes; a symmetric copy of its lower triangle) of a
+//   second cross kernel, built with the points contiguous
+static int qgrad_impl(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var, double* dkta, double* dvar)
 {
     hipStream_t s = c->stream;
     const int64_t N = c->N, ld = c->ld;
     const int D = c->D;
-    if (dvar) {
+    const bool transposed = qt_enabled(c);
+    if (dvar && !transposed) {
         const int e = ensure_inv(c);
         if (e)
             return e;
     }
-    const int64_t mc_max = nm_cols_per_chunk(ld, M), ldt = mc_max + 16;
-    QtBufs b = nm_layout(c, mc_max, false);
-    const int64_t ldq = b.ldq;
-    const bool grads = dkta || dvar;
-    const size_t n_t = dvar ? (size_t)(ldt * N) : 0, n_ki = dvar ? (size_t)(ld * N) : 0;
+    PhaseDrain pd(c);
+    const int64_t mc_max = transposed ? qt_rows_per_chunk(N, M) : nm_cols_per_chunk(ld, M);
+    QtBufs b = transposed ? qt_layout(c, mc_max, N) : nm_layout(c, mc_max, false);
+    const int64_t ldt = transposed ? b.ldq : mc_max + 16; // Wt's leading dimension
+    const bool grads = dkta || dvar, want_z = var || (transposed && dvar), want_ks = transposed || kta || var;
+    const size_t n_t = dvar && !transposed ? (size_t)(ldt * N) : 0, n_ki = dvar && !transposed ? (size_t)(ld * N) : 0;
     size_t n_partg = 0, n_g = 0;
     if (grads)
         qg_extra(c, b.nseg, ldt, mc_max, &n_partg, &n_g);
+    double *dKst2 = nullptr, *dWt = nullptr, *dKi = nullptr, *dPartG = nullptr, *dG = nullptr;
     QueryScratch qs(c);
-    if (const int e = qs.carve(b, 2 * n_t + n_ki + n_partg + n_g))
+    if (const int e = qs.carve([&](Carver& cv) {
+            qt_carve(b, cv);
+            dKst2 = cv.take<double>(n_t); // the cross kernel with the points contiguous
+            dWt = cv.take<double>(n_t);
+            dKi = cv.take<double>(n_ki);
+            dPartG = cv.take<double>(n_partg);
+            dG = cv.take<double>(n_g);
+        }))
         return e;
-    double* dKst = b.dKvv + mc_max; // the cross kernel with the points contiguous
-    double* dWt = dKst + n_t;
-    double* dKi = dWt + n_t;
-    double* dPartG = dKi + n_ki;
-    double* dG = dPartG + n_partg;
-    if (dvar)
+    if (n_ki)
         kinv_operand(c, dKi);
+    chunk_begin(c, b, want_z);
     int rc = GPE_OK;
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
         Marks mk(c->pool, s, c->prof);
         mk.mark();
-        chunk_head(c, b, Xq + m0 * D, true, mc, kta || var, kta != nullptr, kta, m0, M);
-        if (var) {
-            trsm_left_blocked(c, c->dA, b.dKst, ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, b.dQt, ldq, mc, c->kp, b.dKvv);
-            launch_col_var(s, b.dKst, ld, N, mc, b.dKvv, b.dVar); // gp.hpp:621
+        chunk_head(c, b, Xq + m0 * D, true, mc, want_ks, kta != nullptr, kta, m0, M);
+        ZView z;
+        if (want_z)
+            z = chunk_solve(c, b, mc);
+        if (var) { // (before Zt is consumed below)
+            chunk_var(c, b, mc, z);
             hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
         mk.mark();
-        if (dvar) {
+        const double* Wt = nullptr;
+        if (dvar && transposed) {
+            qt_backward(c, b, mc);
+            Wt = b.dKst;
+        }
+        else if (dvar) {
             {
                 PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-                launch_build_Ks(s, b.dQt, ldq, mc, c->dXt, ld, N, c->kp, dKst, ldt); // k is symmetric: the transposed block
+                launch_build_Ks(s, b.dQt, b.ldq, mc, c->dXt, ld, N, c->kp, dKst2, ldt); // k is symmetric: the transposed block
             }
-            times_kinv(c, dKi, dKst, dWt, ldt, mc);
+            times_kinv(c, dKi, dKst2, dWt, ldt, mc);
+            Wt = dWt;
         }
         mk.mark();
         if (grads)
-            qg_columns(c, b.dQt, ldq, mc, mc_max, dvar ? dWt : nullptr, ldt, b.nseg, dPartG, dG, dkta, dvar, m0, M);
+            qg_columns(c, b.dQt, b.ldq, mc, mc_max, Wt, ldt, b.nseg, dPartG, dG, dkta, dvar, m0, M);
         mk.mark();
-        if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-            c->err = "query_batch_grad: stream sync failed";
-            rc = GPE_ERR_HIP;
-        }
+        rc = stream_wait(c, "query_batch_grad", true);
         qg_collect(c, mk);
     }
-    drain_phases(c);
     return rc;
 }
 
@@ -212,9 +174,7 @@ int gpe_query_batch_grad(gpe_handle c, const double* Xq, int64_t M, double* kta,
     digest_kernel(c);
     for (double& ms : c->qgrad_ms)
         ms = 0.0;
-    if (qt_enabled(c))
-        return qgrad_transposed(c, Xq, M, kta, var, dkta, dvar);
-    return qgrad_by_inverse(c, Xq, M, kta, var, dkta, dvar);
+    return qgrad_impl(c, Xq, M, kta, var, dkta, dvar);
 }
 
 int gpe_query_grad_phase_ms(gpe_handle c, double* ms3)

@@ -12,9 +12,20 @@
 // of the direct-to-LDS matrix-core kernel (gemm.hip, k_gemm_glds), as K^-1's U = L^-T (ensure_inv).  The N x M layout
 // (rounds 1-2, still the path for caller-supplied cross kernels) has the right-hand sides k-contiguous and ran its
 // M N^2 flops through the register-staged kernel: 38 TFLOP/s at N = 16384 against the 53 of the factorisation's updates.
-// The helpers below are what every query-side call is built from (qgrad.hpp, pathwise.hpp, joint.hpp, append.hpp, sparse.hpp,
-// sparse_grad.hpp, included behind this file): the layout decision, the chunk size, the buffers, a chunk's head, the panel solve,
-// K^-1 as an operand, the scratch's lease and the phase timer.
+// The helpers below are what every query-side call is built from (qgrad.hpp, pathwise.hpp, joint.hpp, select.hpp, kg.hpp, append.hpp,
+// sparse.hpp, sparse_grad.hpp, included behind this file).  A new one is written against these and names no layout itself:
+//   qt_enabled / qt_serves, qt_rows_per_chunk / nm_cols_per_chunk, qt_layout / nm_layout / served_layout   which layout, how many
+//                                   points, its buffers
+//   QueryScratch::carve(regions)    the call's lease of gpe_ctx::dQuery: the chunk buffers (qt_carve) and every region of the call's
+//                                   own, each declared once with its type and count (Carver, carve.h)
+//   PhaseDrain, Marks, stream_wait  the phase records drained on every way out, the call's own timer, the host's wait
+//   chunk_begin(c, b, want_z)       once per call, in front of the first chunk whose Z is wanted
+//   chunk_head(c, b, X, ...)        per chunk: points -> SoA -> cross kernel (-> kta)
+//   chunk_solve(c, b, mc) -> ZView  Z = L^-1 Ks in the chunk's layout; the view says where it lies and how (z_operands: as the
+//                                   operands of a matrix-core product over the samples, or over the points)
+//   chunk_var(c, b, mc, z, ...)     var = k(v, v) - |z|^2 per point
+// Below these, for what is particular to one layout: qt_panels, qt_forward (also against another context's factor), qt_backward
+// (qgrad.hpp), kinv_operand / times_kinv, trsm_left_blocked.
 
 // Which layout.  The transposed one serves a context whose outer panels are what the one-launch panel inverses take (inv.hip) and
 // that has at least one of them; the marginal calls (query, gradients, path sets) also obey GPE_QUERY_T, read once per process.
@@ -47,7 +58,7 @@ struct QtBufs {
     bool transposed = true; // false: the N x M layout (nm_layout)
     int64_t mc_max = 0, ldq = 0, npan = 0, zcols = 0;
     int nseg = 1, qtile = 128;
-    size_t n_qrm = 0, n_qt = 0, n_kst = 0, n_zt = 0, n_xp = 0, n_part = 0, n_kta = 0, doubles = 0;
+    size_t n_qrm = 0, n_qt = 0, n_kst = 0, n_zt = 0, n_xp = 0, n_part = 0, n_kta = 0;
     double *dQrm = nullptr, *dQt = nullptr, *dKst = nullptr, *dZt = nullptr, *dXp = nullptr, *dPart = nullptr, *dKta = nullptr, *dVar = nullptr,
            *dKvv = nullptr;
 };
@@ -70,21 +81,21 @@ static QtBufs qt_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols, int64_t
     b.n_xp = (size_t)(b.npan * nbo * nbo);
     b.n_part = (size_t)b.nseg * std::max(P, 1) * (size_t)b.ldq;
     b.n_kta = (size_t)(mc_max * P);
-    b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_xp + b.n_part + b.n_kta + 2 * (size_t)mc_max;
     b.qtile = qt_tile(N);
     return b;
 }
-static void qt_carve(QtBufs& b, double* base)
+// b's regions, in the order they lie in the scratch (a region of the call's own list: QueryScratch::carve)
+static void qt_carve(QtBufs& b, Carver& cv)
 {
-    b.dQrm = base;
-    b.dQt = b.dQrm + b.n_qrm;
-    b.dKst = b.dQt + b.n_qt; // the cross kernel, then the running right-hand side Acc
-    b.dZt = b.dKst + b.n_kst;
-    b.dXp = b.dZt + b.n_zt;
-    b.dPart = b.dXp + b.n_xp;
-    b.dKta = b.dPart + b.n_part;
-    b.dVar = b.dKta + b.n_kta;
-    b.dKvv = b.dVar + b.mc_max;
+    b.dQrm = cv.take<double>(b.n_qrm);
+    b.dQt = cv.take<double>(b.n_qt);
+    b.dKst = cv.take<double>(b.n_kst); // the cross kernel, then the running right-hand side Acc
+    b.dZt = cv.take<double>(b.n_zt);
+    b.dXp = cv.take<double>(b.n_xp);
+    b.dPart = cv.take<double>(b.n_part);
+    b.dKta = cv.take<double>(b.n_kta);
+    b.dVar = cv.take<double>((size_t)b.mc_max);
+    b.dKvv = cv.take<double>((size_t)b.mc_max);
 }
 // The N x M layout in the same buffers — fewer samples than one outer panel,
 // GPE_QUERY_T=0, caller-supplied cross kernels: Kst holds Ks (ld x mc_max, the samples contiguous) and is solved in place
@@ -98,8 +109,12 @@ static QtBufs nm_layout(const gpe_ctx* c, int64_t mc_max, bool second)
     b.n_kst = (size_t)(c->ld * mc_max);
     b.n_zt = second ? b.n_kst : 0;
     b.n_xp = b.n_part = 0;
-    b.doubles = b.n_qrm + b.n_qt + b.n_kst + b.n_zt + b.n_kta + 2 * (size_t)mc_max;
     return b;
+}
+// The layout that serves the model, GPE_QUERY_T not asked (the joint posterior, batch selection, the knowledge gradient, the sparse model)
+static QtBufs served_layout(const gpe_ctx* c, int64_t mc_max, int64_t zcols, bool second = false)
+{
+    return qt_serves(c) ? qt_layout(c, mc_max, zcols) : nm_layout(c, mc_max, second);
 }
 extern "C++" {
 namespace { // (file-local types with member functions: nothing of them is exported)
@@ -115,19 +130,39 @@ struct QueryScratch {
         if (sizeof(double) * c->dQuery.capacity() > ((size_t)64 << 20))
             c->dQuery.reset();
     }
-    int reserve(size_t doubles)
+    // room for the regions the call lists (carve.h: counted, reserved, then placed — by the same list), from the scratch's start
+    int carve(const std::function<void(Carver&)>& regions)
     {
-        HIPCHK(c, c->dQuery.reserve(doubles));
+        Carver count;
+        regions(count);
+        HIPCHK(c, c->dQuery.reserve(count.doubles()));
+        Carver place(c->dQuery.get());
+        regions(place);
         return GPE_OK;
     }
-    // room for b and `extra` doubles behind it (from b.dKvv + b.mc_max on); b carved
-    int carve(QtBufs& b, size_t extra = 0)
+    int carve(QtBufs& b) // (a call with the chunk buffers alone)
     {
-        const int e = reserve(b.doubles + extra);
-        if (e == GPE_OK)
-            qt_carve(b, c->dQuery);
-        return e;
+        return carve([&b](Carver& cv) { qt_carve(b, cv); });
     }
+};
+
+// The phase records of the call (PhaseScope: timed events in c->pending while profiling is on) added up and their events returned
+// on every way out of it, an early return after a HIP error included.  Declared in front of the call's QueryScratch and Marks.
+struct PhaseDrain {
+    gpe_ctx* c;
+    explicit PhaseDrain(gpe_ctx* c_) : c(c_) {}
+    PhaseDrain(const PhaseDrain&) = delete;
+    ~PhaseDrain() { drain_phases(c); }
+};
+
+// Where a chunk's Z = L^-1 Ks lies (chunk_solve): element (point m, sample i) at p[m + i ld] — or, kmajor, at p[m ld + i]: the
+// samples, the k index of every product with Z, contiguous
+struct ZView {
+    const double* p = nullptr;
+    int64_t ld = 0;
+    int kmajor = 0;
+    int64_t sm() const { return kmajor ? ld : 1; } // the strides of a point and of a sample
+    int64_t si() const { return kmajor ? 1 : ld; }
 };
 
 // The call's own phases for the *_phase_ms exports: boundaries recorded on one stream with events of one pool (the handle's, under
@@ -164,6 +199,28 @@ struct Marks {
 };
 } // namespace
 } // extern "C++"
+
+// The host waits for stream s; last_error: what a launch since the last wait left behind is consulted too (each call's own choice).
+// On failure err = "<what>: stream sync failed" and GPE_ERR_HIP.
+static int stream_wait(hipStream_t s, std::string& err, const char* what, bool last_error)
+{
+    if (hipStreamSynchronize(s) == hipSuccess && (!last_error || hipGetLastError() == hipSuccess))
+        return GPE_OK;
+    err = std::string(what) + ": stream sync failed";
+    return GPE_ERR_HIP;
+}
+static int stream_wait(gpe_ctx* c, const char* what, bool last_error) { return stream_wait(c->stream, c->err, what, last_error); }
+
+// Z views as the operands of C (-)= A B^T over the samples (k = N) — or, over_points, over the chunk's points (k = mc)
+static void z_operands(GemmArgs& g, const ZView& a, const ZView& b, bool over_points = false)
+{
+    g.A = a.p;
+    g.lda = a.ld;
+    g.a_kmajor = over_points ? !a.kmajor : a.kmajor;
+    g.B = b.p;
+    g.ldb = b.ld;
+    g.b_kmajor = over_points ? !b.kmajor : b.kmajor;
+}
 
 // X_p of every panel, compact (in front of the first chunk whose Zt is wanted)
 static void qt_panels(gpe_ctx* c, const QtBufs& b)
@@ -250,13 +307,38 @@ static void chunk_head(gpe_ctx* c, const QtBufs& b, const double* X, bool x_on_h
         for (int p = 0; p < P; ++p)
             hipMemcpyAsync(kta + m0 + (int64_t)p * M, b.dKta + (int64_t)p * b.mc_max, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
 }
-// one chunk of the transposed layout (points on the host): its head and, want_z, Zt = Kst L^-T (Kst is destroyed)
-static void qt_chunk(gpe_ctx* c, const QtBufs& b, const double* Xq_chunk, int64_t mc, bool want_kta, double* kta, int64_t m0, int64_t M,
-                     bool want_z)
+// Once per call, in front of the first chunk whose Z is wanted: what chunk_solve needs beside the factor
+static void chunk_begin(gpe_ctx* c, const QtBufs& b, bool want_z)
 {
-    chunk_head(c, b, Xq_chunk, true, mc, true, want_kta, kta, m0, M);
-    if (want_z)
+    if (b.transposed && want_z)
+        qt_panels(c, b);
+}
+// Z = L^-1 Ks for the mc points of the chunk whose cross kernel (or whatever a caller put in its place) is in b.dKst, which is
+// destroyed (gp.hpp:620): by the panels into b.dZt, or by the blocked solve in place
+static ZView chunk_solve(gpe_ctx* c, const QtBufs& b, int64_t mc)
+{
+    if (b.transposed) {
         qt_forward(c, b, mc);
+        return ZView{b.dZt, b.ldq, 0};
+    }
+    trsm_left_blocked(c, c->dA, b.dKst, c->ld, c->N, mc, false, GPE_PH_QUERY);
+    return ZView{b.dKst, c->ld, 1};
+}
+// var[m] = kvv[m] - sum_i z(m, i)^2 over c's N samples (gp.hpp:621), on c's stream.  kvv null: k(v_m, v_m) of the chunk's points,
+// computed here into b.dKvv; else the caller's (zeros: minus the squared norm alone).  var null: b.dVar.
+static void chunk_var(gpe_ctx* c, const QtBufs& b, int64_t mc, const ZView& z, const double* kvv = nullptr, double* var = nullptr)
+{
+    PhaseScope ps(c, GPE_PH_QUERY, 2.0 * c->N * mc);
+    if (!kvv) {
+        launch_kvv(c->stream, b.dQt, b.ldq, mc, c->kp, b.dKvv);
+        kvv = b.dKvv;
+    }
+    if (!var)
+        var = b.dVar;
+    if (z.kmajor)
+        launch_col_var(c->stream, z.p, z.ld, c->N, mc, kvv, var);
+    else
+        launch_row_var_t(c->stream, z.p, z.ld, c->N, mc, kvv, var, b.dPart, b.ldq, b.nseg);
 }
 
 // K^-1 as an operand where the transposed layout does not serve (gradients, path sets): a full symmetric copy at dKi (ld x N) of
@@ -285,43 +367,13 @@ static void times_kinv(gpe_ctx* c, const double* dKi, const double* dRt, double*
     launch_gemm_sub(c->stream, g);
 }
 
-static int query_transposed(gpe_ctx* c, const double* Xq, int64_t M, double* kta, double* var)
-{
-    hipStream_t s = c->stream;
-    const int64_t N = c->N;
-    const int D = c->D;
-    const int64_t mc_max = qt_rows_per_chunk(N, M);
-    QtBufs b = qt_layout(c, mc_max, N);
-    QueryScratch qs(c);
-    if (const int e = qs.carve(b))
-        return e;
-    int rc = GPE_OK;
-    if (var)
-        qt_panels(c, b);
-    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
-        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        qt_chunk(c, b, Xq + m0 * D, mc, kta != nullptr, kta, m0, M, var != nullptr);
-        if (var) {
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            launch_kvv(s, b.dQt, b.ldq, mc, c->kp, b.dKvv);
-            launch_row_var_t(s, b.dZt, b.ldq, N, mc, b.dKvv, b.dVar, b.dPart, b.ldq, b.nseg); // gp.hpp:621
-            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
-        }
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            c->err = "query_batch: stream sync failed";
-            rc = GPE_ERR_HIP;
-        }
-    }
-    drain_phases(c);
-    return rc;
-}
-
 // shared by gpe_query_batch (cross kernel built on the device from Xq) and gpe_query_batch_cross
 // (cross kernel handed over by the caller): kta = Ks^T alpha, var = kvv - colsum((L^-1 Ks)^2)
 static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_t M, double* kta, double* var)
 {
     hipStream_t s = c->stream;
     digest_kernel(c);
+    PhaseDrain pd(c);
     const int64_t N = c->N, ld = c->ld;
     const int D = c->D, P = c->P;
     if (c->small_path && Xq && N <= small_max_n() && M <= 8 && (int64_t)M * D <= 1024 && P <= GPE_MAX_P) {
@@ -351,8 +403,7 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
             launch_small_query(s, q, c->kp, lam_params(c));
         }
         ++c->small_calls;
-        int rc = small_wait(c, (int)M, q.seq_val);
-        drain_phases(c);
+        const int rc = small_wait(c, (int)M, q.seq_val);
         if (rc)
             return rc;
         if (kta)
@@ -366,53 +417,42 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
     // blocked matrix solve, whose ~2 N/64 dependent matrix-core launches are all launch floor there
     static const bool sweep_ok = env_not_zero("GPE_QUERY_SWEEP");
     const bool few = sweep_ok && c->flow_solve && M <= GPE_MAX_P && (N + NB - 1) / NB <= 256;
-    if (Xq && !few && qt_enabled(c))
-        return query_transposed(c, Xq, M, kta, var);
-    const int64_t mc_max = few ? GPE_MAX_P : nm_cols_per_chunk(ld, M);
-    QtBufs b = nm_layout(c, mc_max, few); // (the sweep's Z beside Ks)
+    // the transposed layout for the device's own cross kernel; the N x M one for a caller's, for the sweep (its Z beside Ks) and
+    // where the transposed one does not serve
+    const bool transposed = Xq && !few && qt_enabled(c);
+    const int64_t mc_max = few ? GPE_MAX_P : transposed ? qt_rows_per_chunk(N, M) : nm_cols_per_chunk(ld, M);
+    QtBufs b = transposed ? qt_layout(c, mc_max, N) : nm_layout(c, mc_max, few);
     QueryScratch qs(c);
     if (const int e = qs.carve(b))
         return e;
-    const int64_t ldq = b.ldq;
-    double *dQt = b.dQt, *dKs = b.dKst, *dZ = b.dZt, *dVar = b.dVar, *dKvv = b.dKvv;
     int rc = GPE_OK;
+    chunk_begin(c, b, var != nullptr);
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
         if (!Xq) // the caller's cross kernel in the place of the device's
-            copy2d_from_host(dKs, ld, KsHost + m0 * N, N, N, mc, s);
+            copy2d_from_host(b.dKst, ld, KsHost + m0 * N, N, N, mc, s);
         chunk_head(c, b, Xq ? Xq + m0 * D : nullptr, true, mc, Xq != nullptr, kta != nullptr, kta, m0, M);
         if (var) {
-            const double* Z = dKs;
+            ZView z;
             if (few) {
                 PhaseScope ps(c, GPE_PH_QUERY, (double)N * N * mc);
-                launch_trsv_fwd_flow(s, c->dA, ld, N, c->dXinv, dKs, ld, dZ, ld, (int)mc, c->dInfo + 1); // gp.hpp:620
-                Z = dZ;
+                launch_trsv_fwd_flow(s, c->dA, ld, N, c->dXinv, b.dKst, ld, b.dZt, ld, (int)mc, c->dInfo + 1); // gp.hpp:620
+                z = ZView{b.dZt, ld, 1};
             }
             else
-                trsm_left_blocked(c, c->dA, dKs, ld, N, mc, false, GPE_PH_QUERY); // gp.hpp:620
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * mc);
-            if (Xq)
-                launch_kvv(s, dQt, ldq, mc, c->kp, dKvv);
-            else
-                hipMemsetAsync(dKvv, 0, sizeof(double) * (size_t)mc, s);
-            launch_col_var(s, Z, ld, N, mc, dKvv, dVar); // gp.hpp:621
-            hipMemcpyAsync(var + m0, dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+                z = chunk_solve(c, b, mc);
+            if (!Xq) // (a caller's cross kernel comes without the points: var is minus the squared norm alone)
+                hipMemsetAsync(b.dKvv, 0, sizeof(double) * (size_t)mc, s);
+            chunk_var(c, b, mc, z, Xq ? nullptr : b.dKvv);
+            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
         }
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            c->err = "query_batch: stream sync failed";
-            rc = GPE_ERR_HIP;
-        }
-        else if (few && var && flow_failed(c)) {
+        rc = stream_wait(c, "query_batch", false);
+        if (rc == GPE_OK && few && var && flow_failed(c)) {
             // the one-launch sweep gave up (never expected): the same chunk through the blocked solve, in place
-            trsm_left_blocked(c, c->dA, dKs, ld, N, mc, false, GPE_PH_QUERY);
-            launch_col_var(s, dKs, ld, N, mc, dKvv, dVar);
-            hipMemcpyAsync(var + m0, dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
-            if (hipStreamSynchronize(s) != hipSuccess) {
-                c->err = "query_batch: stream sync failed";
-                rc = GPE_ERR_HIP;
-            }
+            chunk_var(c, b, mc, chunk_solve(c, b, mc), b.dKvv);
+            hipMemcpyAsync(var + m0, b.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s);
+            rc = stream_wait(c, "query_batch", false);
         }
     }
-    drain_phases(c);
     return rc;
 }

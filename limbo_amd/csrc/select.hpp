@@ -9,60 +9,52 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
     hipStream_t s = c->stream;
     digest_kernel(c);
     const int64_t N = c->N;
-    // Fewer samples than one outer panel: the N x M layout of query_impl,
-    // transposed once into the layout of the rounds
-    const bool transposed = qt_serves(c);
+    PhaseDrain pd(c);
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
     const int64_t mc_max = round_up(M, 64);
-    QtBufs b = transposed ? qt_layout(c, mc_max, N) : nm_layout(c, mc_max, false);
+    QtBufs b = served_layout(c, mc_max, N);
     const int64_t ldz = mc_max + 16; // as QtBufs::ldq of the transposed layout: even (16-byte rows), not a power of two
     const int nch = select_chunks(M, N, cus);
     const int64_t nrows = select_plan(M, N, cus, nullptr, 0);
-    const int64_t nwg = select_fold_groups(M);
-    const size_t n_zt2 = transposed ? 0 : (size_t)(ldz * N);
-    const size_t n_zj = (size_t)round_up(N, 2), n_wj = (size_t)round_up(q, 2);
-    const size_t n_part = (size_t)nch * (size_t)ldz, n_w = (size_t)ldz * (size_t)q, n_mu = (size_t)mc_max;
-    const size_t n_pairs = 2 * (size_t)nwg, n_state = sizeof(SelState) / 8, n_idx = (size_t)q, n_picked = (size_t)mc_max / 2;
     const size_t n_plan = 5 * (size_t)nrows;
+    double *dZt2 = nullptr, *dZj = nullptr, *dWj = nullptr, *dPartV = nullptr, *dW = nullptr, *dMu = nullptr, *dPairs = nullptr, *dScore = nullptr;
+    SelState* dState = nullptr;
+    long long* dIdx = nullptr;
+    int* dPicked = nullptr;
+    int64_t* dPlan = nullptr;
     QueryScratch qs(c);
-    if (const int e = qs.carve(b, n_zt2 + n_zj + n_wj + n_part + n_w + n_mu + n_pairs + n_state + 2 * n_idx + n_picked + n_plan))
+    if (const int e = qs.carve([&](Carver& cv) {
+            qt_carve(b, cv);
+            dZt2 = cv.take<double>(b.transposed ? 0 : (size_t)(ldz * N)); // Z with the points contiguous, where the layout has them not
+            dZj = cv.take<double>((size_t)N);
+            dWj = cv.take<double>((size_t)q);
+            dPartV = cv.take<double>((size_t)nch * (size_t)ldz);
+            dW = cv.take<double>((size_t)ldz * (size_t)q);
+            dMu = cv.take<double>((size_t)mc_max);
+            dPairs = cv.take<double>(2 * (size_t)select_fold_groups(M));
+            dState = cv.take<SelState>(1); // (from here to the end of dPicked: cleared by one fill, below)
+            dIdx = cv.take<long long>((size_t)q);
+            dScore = cv.take<double>((size_t)q);
+            dPicked = cv.take<int>((size_t)mc_max);
+            dPlan = cv.take<int64_t>(n_plan);
+        }))
         return e;
-    double* dZt2 = b.dKvv + b.mc_max; // (an even offset into the scratch: 16-byte aligned, like the pipeline's own Zt)
-    double* dZj = dZt2 + n_zt2;
-    double* dWj = dZj + n_zj;
-    double* dPartV = dWj + n_wj;
-    double* dW = dPartV + n_part;
-    double* dMu = dW + n_w;
-    double* dPairs = dMu + n_mu;
-    SelState* dState = (SelState*)(dPairs + n_pairs);
-    long long* dIdx = (long long*)((double*)dState + n_state);
-    double* dScore = (double*)dIdx + n_idx;
-    int* dPicked = (int*)(dScore + n_idx);
-    int64_t* dPlan = (int64_t*)((double*)dPicked + n_picked);
 
     std::vector<int64_t> plan(n_plan); // (alive until the stream has been waited for, below)
     (void)select_plan(M, N, cus, plan.data(), nrows);
 
     Marks mk(c->pool, s, c->prof);
     const int t0 = mk.mark();
-    if (!transposed) {
-        chunk_head(c, b, Xq, true, M, true, mu_q == nullptr, nullptr, 0, M);
-        trsm_left_blocked(c, c->dA, b.dKst, c->ld, N, M, false, GPE_PH_QUERY); // gp.hpp:620
-        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * M);
-        launch_kvv(s, b.dQt, b.ldq, M, c->kp, b.dKvv);
-        launch_col_var(s, b.dKst, c->ld, N, M, b.dKvv, b.dVar); // gp.hpp:621
-        launch_sel_transpose(s, b.dKst, c->ld, N, M, dZt2, ldz);
+    chunk_begin(c, b, true);
+    chunk_head(c, b, Xq, true, M, true, mu_q == nullptr, nullptr, 0, M);
+    ZView z = chunk_solve(c, b, M);
+    chunk_var(c, b, M, z);
+    if (z.kmajor) { // the rounds read Z with the points contiguous: transposed once
+        launch_sel_transpose(s, z.p, z.ld, N, M, dZt2, ldz);
+        z = ZView{dZt2, ldz, 0};
     }
-    else {
-        qt_panels(c, b);
-        qt_chunk(c, b, Xq, M, mu_q == nullptr, nullptr, 0, M, true);
-        PhaseScope ps(c, GPE_PH_QUERY, 2.0 * N * M);
-        launch_kvv(s, b.dQt, b.ldq, M, c->kp, b.dKvv);
-        launch_row_var_t(s, b.dZt, b.ldq, N, M, b.dKvv, b.dVar, b.dPart, b.ldq, b.nseg); // gp.hpp:621
-    }
-    // (the state words, the score and index vectors and the picked flags are adjacent: one fill)
-    HIPCHK(c, hipMemsetAsync(dState, 0, sizeof(double) * (n_state + 2 * n_idx + n_picked), s));
+    HIPCHK(c, hipMemsetAsync(dState, 0, (size_t)((char*)(dPicked + mc_max) - (char*)dState), s));
     HIPCHK(c, hipMemcpyAsync(dPlan, plan.data(), sizeof(int64_t) * n_plan, hipMemcpyHostToDevice, s));
     if (mu_q)
         HIPCHK(c, hipMemcpyAsync(dMu, mu_q, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, s));
@@ -72,8 +64,8 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
     g.plan = dPlan;
     g.nrows = nrows;
     g.nch = nch;
-    g.Zt = transposed ? b.dZt : dZt2;
-    g.ldz = transposed ? b.ldq : ldz;
+    g.Zt = z.p;
+    g.ldz = z.ld;
     g.N = N;
     g.M = M;
     g.Qt = b.dQt;
@@ -113,11 +105,8 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
     HIPCHK(c, hipMemcpyAsync(hscore.data(), dScore, sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, s));
     if (var_out)
         HIPCHK(c, hipMemcpyAsync(var_out, b.dVar, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, s));
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        c->err = "select_batch: stream sync failed";
-        drain_phases(c);
-        return GPE_ERR_HIP;
-    }
+    if (const int e = stream_wait(c, "select_batch", true))
+        return e;
     // rounds < fail - 1 are complete; round fail - 1 has its pick and score, not its column
     const int rounds = st.fail ? (int)st.fail : q, cols = st.fail ? (int)st.fail - 1 : q;
     for (int r = 0; r < rounds; ++r) {
@@ -128,11 +117,8 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
     }
     if (W && cols > 0) {
         HIPCHK(c, copy2d_to_host(W, ldw, dW, ldz, M, cols, s));
-        if (hipStreamSynchronize(s) != hipSuccess) {
-            c->err = "select_batch: stream sync failed";
-            drain_phases(c);
-            return GPE_ERR_HIP;
-        }
+        if (const int e = stream_wait(c, "select_batch", false))
+            return e;
     }
     const int t3 = mk.mark();
     if (c->prof) {
@@ -140,7 +126,6 @@ static int select_impl(gpe_ctx* c, const double* Xq, int64_t M, int q, int rule,
         c->select_ms[1] = mk.ms(t1, t2);
         c->select_ms[2] = mk.ms(t2, t3);
     }
-    drain_phases(c);
     return (int)st.fail;
 }
 

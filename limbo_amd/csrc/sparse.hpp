@@ -61,28 +61,19 @@ bool sp_use_gram_kernel(int64_t M, int cus)
     return nt * (nt + 1) / 2 < 2 * (int64_t)cus;
 }
 
-// the layout of a chunk (query.hpp): transposed — points contiguous, from one outer panel of pseudo-inputs on — or N x M with
-// room for a weighted copy beside Ks
-QtBufs sp_layout(const gpe_ctx* c, int64_t mc_max) { return qt_serves(c) ? qt_layout(c, mc_max, c->N) : nm_layout(c, mc_max, true); }
+// the layout of a chunk (query.hpp): the one that serves the inner model, with room for a second matrix beside Ks in either
+QtBufs sp_layout(const gpe_ctx* c, int64_t mc_max) { return served_layout(c, mc_max, c->N, true); }
 
 // the chunk's points (device, row-major mc x D) -> SoA, the cross kernel against the pseudo-inputs (spgp.hpp:396 / :597), V by the
 // inner model's factor (:398 / :598) — a chunk of the batched query with the inner model as the model.  Its phases record nothing:
-// the inner context's profiling is never on.  Returns V's place: element (n, i) at Z[n sn + i si].
-const double* sp_v_chunk(gpe_sp_ctx* h, const QtBufs& b, const double* dXrm, int64_t mc, int64_t* sn, int64_t* si)
+// the inner context's profiling is never on.  Returns V's place (needs chunk_begin).
+ZView sp_v_chunk(gpe_sp_ctx* h, const QtBufs& b, const double* dXrm, int64_t mc)
 {
-    gpe_ctx* c = h->in;
-    chunk_head(c, b, dXrm, false, mc, true, false, nullptr, 0, 0);
-    if (b.transposed) {
-        qt_forward(c, b, mc);
-        *sn = 1;
-        *si = b.ldq;
-        return b.dZt;
-    }
-    trsm_left_blocked(c, c->dA, b.dKst, c->ld, c->N, mc, false, GPE_PH_QUERY);
-    *sn = c->ld;
-    *si = 1;
-    return b.dKst;
+    chunk_head(h->in, b, dXrm, false, mc, true, false, nullptr, 0, 0);
+    return chunk_solve(h->in, b, mc);
 }
+// the chunk's other matrix (sp_layout): where V is not
+double* sp_beside(const QtBufs& b, const ZView& z) { return z.p == b.dZt ? b.dKst : b.dZt; }
 
 // (re)shape the scratch context for order M and P right-hand sides
 int sp_scratch(gpe_sp_ctx* h)
@@ -131,7 +122,6 @@ int sp_compute_locked(gpe_sp_ctx* h)
     const int64_t chunk = sp_chunk(M, N);
     const bool own_gram = sp_use_gram_kernel(M, cus);
     QtBufs b = sp_layout(in, chunk);
-    const bool transposed = b.transposed;
     QueryScratch qs(in);
     if (const int e = qs.carve(b)) {
         h->err = "sparse GP: " + in->err;
@@ -155,16 +145,16 @@ int sp_compute_locked(gpe_sp_ctx* h)
     HIPCHK(h, hipMemsetAsync(sc->dOm, 0, sizeof(double) * (size_t)(sc->ld * P), s)); // r
     if (!own_gram)
         launch_zero2d(s, dA, lda, Mpad, Mpad);
-    if (transposed)
-        qt_panels(in, b);
+    chunk_begin(in, b, true);
     Marks mk(in->pool, s, h->prof); // per chunk three phases — V, ep and r, the Gram — of two boundaries each
     const int64_t nt = (M + 63) / 64, tiles = nt * (nt + 1) / 2;
     int64_t row0 = 0, slot0 = 0;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, N - n0);
-        int64_t sn = 0, si = 0;
         mk.mark();
-        const double* Z = sp_v_chunk(h, b, h->dX + n0 * D, mc, &sn, &si);
+        const ZView z = sp_v_chunk(h, b, h->dX + n0 * D, mc);
+        const double* Z = z.p;
+        const int64_t sn = z.sm(), si = z.si();
         mk.mark();
         mk.mark();
         launch_sp_ep(s, Z, sn, si, mc, M, h->c, h->sig, h->dEp + n0, h->dW);
@@ -185,15 +175,12 @@ int sp_compute_locked(gpe_sp_ctx* h)
         }
         else {
             // the composed path: a weighted copy of V, then the engine's general product on the k-contiguous operands
-            double* Zw = transposed ? b.dKst : b.dZt;
+            double* Zw = sp_beside(b, z);
             launch_sp_scale(s, Z, sn, si, mc, M, h->dW, Zw);
             GemmArgs g{};
             g.C = dA;
             g.ldc = lda;
-            g.A = Zw;
-            g.B = Z;
-            g.lda = g.ldb = transposed ? b.ldq : in->ld;
-            g.a_kmajor = g.b_kmajor = transposed ? 1 : 0;
+            z_operands(g, ZView{Zw, z.ld, z.kmajor}, z, true); // V^T diag(w) V: the k index is the chunk's points
             g.m = g.n = M;
             g.k = mc;
             g.tri = 1;
@@ -207,10 +194,8 @@ int sp_compute_locked(gpe_sp_ctx* h)
     launch_sp_sums(s, h->dEp, N, h->dY, N, P, h->dSums);
     std::vector<double> sums((size_t)P + 1);
     HIPCHK(h, hipMemcpyAsync(sums.data(), h->dSums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, s));
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) {
-        h->err = "sparse GP: stream sync failed";
-        return GPE_ERR_HIP;
-    }
+    if (const int e = stream_wait(s, h->err, "sparse GP", true))
+        return e;
     if (h->prof)
         for (int ph = 0; ph < 3; ++ph) {
             h->ms[ph] = 0.0;
@@ -262,25 +247,25 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     // points per chunk: from M alone (a prediction must not depend on the batch around it)
     const int64_t mc_max = std::min<int64_t>(sparse_default_chunk(M), 16384);
     QtBufs b = sp_layout(in, mc_max);
-    const bool transposed = b.transposed;
-    // behind the query buffers: v1, v2, zero (mc_max each), mu (mc_max x P), s2, the partial sums of the P outputs
-    const size_t n_extra = 4 * (size_t)mc_max + (size_t)mc_max * P + (size_t)b.nseg * P * (size_t)b.ldq;
+    double *dV1 = nullptr, *dV2 = nullptr, *dZero = nullptr, *dS2 = nullptr, *dMu = nullptr, *dPartP = nullptr;
     QueryScratch qs(in);
-    if (const int e = qs.carve(b, n_extra)) {
+    if (const int e = qs.carve([&](Carver& cv) {
+            qt_carve(b, cv);
+            dV1 = cv.take<double>((size_t)mc_max);
+            dV2 = cv.take<double>((size_t)mc_max);
+            dZero = cv.take<double>((size_t)mc_max);
+            dS2 = cv.take<double>((size_t)mc_max);
+            dMu = cv.take<double>((size_t)mc_max * P);
+            dPartP = cv.take<double>((size_t)b.nseg * P * (size_t)b.ldq); // the partial sums of the P outputs
+        })) {
         h->err = "sparse GP: " + in->err;
         return e;
     }
-    double* dV1 = b.dKvv + b.mc_max;
-    double* dV2 = dV1 + mc_max;
-    double* dZero = dV2 + mc_max;
-    double* dS2 = dZero + mc_max;
-    double* dMu = dS2 + mc_max;
-    double* dPartP = dMu + (size_t)mc_max * P;
     Marks mk(in->pool, s, h->prof);
     mk.mark();
     HIPCHK(h, hipMemsetAsync(dZero, 0, sizeof(double) * (size_t)mc_max, s));
-    if (transposed) {
-        qt_panels(in, b);
+    chunk_begin(in, b, true);
+    if (b.transposed) { // Lm's panel inverses beside L's, for the second solve
         const int64_t npan = (M + NBO - 1) / NBO;
         HIPCHK(h, h->dXp2.reserve((size_t)(npan * NBO * NBO)));
         launch_inv_panels(s, sc->dA, sc->ld, M, NBO, sc->dXinv, h->dXp2, 0, nullptr, 0);
@@ -288,20 +273,18 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
     int rc = GPE_OK;
     for (int64_t t0 = 0; t0 < T && rc == GPE_OK; t0 += mc_max) {
         const int64_t tc = std::min<int64_t>(mc_max, T - t0);
-        int64_t sn = 0, si = 0;
         HIPCHK(h, hipMemcpyAsync(b.dQrm, Xt + t0 * D, sizeof(double) * (size_t)(tc * D), hipMemcpyHostToDevice, s));
-        const double* Z = sp_v_chunk(h, b, b.dQrm, tc, &sn, &si); // lst (spgp.hpp:597-598)
-        launch_kvv(s, b.dQt, b.ldq, tc, in->kp, b.dKvv);                      // _k_diag (:630-634)
+        const ZView z = sp_v_chunk(h, b, b.dQrm, tc); // lst (spgp.hpp:597-598)
+        chunk_var(in, b, tc, z, nullptr, dV1);        // _k_diag (:630-634), c - |lst|^2
+        // lmst = Lm^-1 lst (:599), into Kst, by the scratch context's factor; then - |lmst|^2 and the mean (:604)
         hipStream_t s2nd = s;
-        if (transposed) {
-            launch_row_var_t(s, Z, b.ldq, M, tc, b.dKvv, dV1, b.dPart, b.ldq, b.nseg);   // c - |lst|^2
-            qt_forward(in, b, tc, sc, h->dXp2, b.dZt, b.dKst);                           // lmst (:599), into Kst
-            launch_row_var_t(s, b.dKst, b.ldq, M, tc, dZero, dV2, b.dPart, b.ldq, b.nseg); // - |lmst|^2
+        if (!z.kmajor) {
+            qt_forward(in, b, tc, sc, h->dXp2, b.dZt, b.dKst);
+            chunk_var(in, b, tc, ZView{b.dKst, b.ldq, 0}, dZero, dV2);
             if (mu)
-                launch_kta_t(s, b.dKst, b.ldq, M, tc, h->dBet, Mpad, P, dMu, mc_max, dPartP, b.ldq, b.nseg); // :604
+                launch_kta_t(s, b.dKst, b.ldq, M, tc, h->dBet, Mpad, P, dMu, mc_max, dPartP, b.ldq, b.nseg);
         }
         else {
-            launch_col_var(s, Z, in->ld, M, tc, b.dKvv, dV1);
             // the blocked solve launches on its context's stream: hand over to the scratch context's
             if (hipStreamSynchronize(s) != hipSuccess) {
                 rc = GPE_ERR_HIP;
@@ -309,7 +292,7 @@ int sp_predict_locked(gpe_sp_ctx* h, const double* Xt, int64_t T, double* mu, do
             }
             s2nd = sc->stream;
             trsm_left_blocked(sc, sc->dA, b.dKst, in->ld, M, tc, false, GPE_PH_QUERY);
-            launch_col_var(s2nd, b.dKst, in->ld, M, tc, dZero, dV2);
+            chunk_var(sc, b, tc, ZView{b.dKst, in->ld, 1}, dZero, dV2);
             if (mu)
                 launch_kta(s2nd, b.dKst, in->ld, M, tc, h->dBet, Mpad, P, dMu, mc_max);
         }

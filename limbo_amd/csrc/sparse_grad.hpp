@@ -150,17 +150,15 @@ int sp_grad_locked(gpe_sp_ctx* h, double* d_xb, double* d_hp)
         h->err = "sparse GP gradient: " + in->err;
         return e;
     }
-    if (bq.transposed)
-        qt_panels(in, bq);
+    chunk_begin(in, bq, true);
     const int64_t nt = (M + 63) / 64, tiles = nt * (nt + 1) / 2;
     int64_t row0 = 0, slot0 = 0, blk0 = 0;
     for (int64_t n0 = 0; n0 < N; n0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, N - n0);
         mk.mark();
-        int64_t sn = 0, si = 0;
-        const double* Z = sp_v_chunk(h, bq, h->dX + n0 * D, mc, &sn, &si); // V (:396-398)
+        const ZView z = sp_v_chunk(h, bq, h->dX + n0 * D, mc); // V (:396-398)
         launch_sp_grs(s, h->dEp + n0, mc, b.rs);
-        launch_sp_gvt(s, Z, sn, si, mc, M, b.rs, b.B1t, ldq); // V~^T (:401), for now where B1t will be
+        launch_sp_gvt(s, z.p, z.sm(), z.si(), mc, M, b.rs, b.B1t, ldq); // V~^T (:401), for now where B1t will be
         for (int q = 0; q < 3; ++q) { // ILVt = V~t Lm^-T (:483), IQt = V~t L^-1 (:504 invLV), B1t = ILVt Lt^-1 (:502)
             GemmArgs g{};
             g.C = q == 0 ? b.ILVt : q == 1 ? b.IQt : b.B1t;
