@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <vector>
 #include <limbo/tools/macros.hpp>
 
 namespace limbo {
@@ -148,6 +149,57 @@ namespace limbo_amd {
             const double d = knn - s;
             row[n] = std::sqrt(d);
             return d > 0.0 ? 0 : (int)(n + 1);
+        }
+        /// Rows and columns R[0] < R[1] < ... < R[q-1] leave the factor L (order n, ldl): out (order n - q, ldo, strict upper
+        /// triangle zeroed) = chol(K[S, S]), S the kept set in its order (include/gpe_remove.h).  The column sweep: a removed
+        /// column's part below its diagonal becomes an update vector, a kept column takes one Givens rotation with every live
+        /// vector, chosen from (L[c, c], u[c]) — a positive rank-1 update each, so no pivot can fail.  NaNs propagate.
+        inline void remove_rows(const double* L, int64_t n, int64_t ldl, const int64_t* R, int64_t q, double* out, int64_t ldo)
+        {
+            std::vector<double> U((size_t)(n * q), 0.0), col((size_t)n);
+            std::vector<int64_t> newrow((size_t)n);
+            for (int64_t r = 0, k = 0; r < n; ++r) {
+                if (k < q && R[k] == r) {
+                    newrow[(size_t)r] = -1;
+                    ++k;
+                }
+                else
+                    newrow[(size_t)r] = r - k;
+            }
+            int64_t born = 0, cn = 0;
+            for (int64_t c = 0; c < n; ++c) {
+                const double* cj = L + c * ldl;
+                if (newrow[(size_t)c] < 0) {
+                    double* u = U.data() + born * n;
+                    for (int64_t r = c + 1; r < n; ++r)
+                        u[r] = cj[r];
+                    ++born;
+                    continue;
+                }
+                for (int64_t r = c; r < n; ++r)
+                    col[(size_t)r] = cj[r];
+                for (int64_t v = 0; v < born; ++v) {
+                    double* u = U.data() + v * n;
+                    const double d = col[(size_t)c], uc = u[c];
+                    if (uc == 0.0)
+                        continue;
+                    const double h = std::hypot(d, uc), cs = d / h, sn = uc / h;
+                    col[(size_t)c] = h;
+                    u[c] = 0.0;
+                    for (int64_t r = c + 1; r < n; ++r) {
+                        const double x = col[(size_t)r], y = u[r];
+                        col[(size_t)r] = cs * x + sn * y;
+                        u[r] = -sn * x + cs * y;
+                    }
+                }
+                double* oj = out + cn * ldo;
+                for (int64_t i = 0; i < cn; ++i)
+                    oj[i] = 0.0;
+                for (int64_t r = c; r < n; ++r)
+                    if (newrow[(size_t)r] >= 0)
+                        oj[newrow[(size_t)r]] = col[(size_t)r];
+                ++cn;
+            }
         }
         /// The score of one candidate in greedy batch selection (include/gpe_batch_select.h): rule 0 UCB (param = beta), 1 EI
         /// (param = f+ + jitter; acqui/ei.hpp: _value), 2 the variance; var_add enters behind the clamp of gp.hpp:623

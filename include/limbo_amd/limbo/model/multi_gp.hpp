@@ -8,7 +8,9 @@
 // file named above.  The implementation behind the interface is this project's own.
 #ifndef LIMBO_MODEL_MULTI_GP_HPP
 #define LIMBO_MODEL_MULTI_GP_HPP
+#include <algorithm>
 #include <cassert>
+#include <cstddef>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -97,6 +99,22 @@ namespace limbo {
                         obs[i].push_back(limbo::tools::make_vector(observations[j](i) - mv(i)));
                 }
                 limbo::tools::par::loop(0, _dim_out, [&](size_t i) { _gp_models[i].add_samples(samples, obs[i]); });
+            }
+
+            /// The samples at `indices` (any order, distinct) leave every member GP (model::GP::remove_samples).  The members keep
+            /// the targets they were given (observation minus the mean functor's value at the time): for a mean that does not
+            /// depend on the observations this is compute() on the remaining samples, to rounding.
+            void remove_samples(const std::vector<size_t>& indices)
+            {
+                if (indices.empty() || _gp_models.size() == 0)
+                    return;
+                std::vector<size_t> R(indices);
+                std::sort(R.begin(), R.end());
+                assert(R.back() < _observations.size() && std::adjacent_find(R.begin(), R.end()) == R.end());
+                for (size_t k = R.size(); k-- > 0;)
+                    _observations.erase(_observations.begin() + (std::ptrdiff_t)R[k]);
+                _update_mean_observation();
+                limbo::tools::par::loop(0, _dim_out, [&](size_t i) { _gp_models[i].remove_samples(R); });
             }
 
             /// (mu, one sigma^2 per output)

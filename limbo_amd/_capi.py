@@ -21,6 +21,8 @@ ENGINE_SO = _PKG / "libgpengine.so"
 KERNEL_SE_ARD, KERNEL_MATERN52, KERNEL_MATERN32, KERNEL_EXP, KERNEL_HOST_K = range(5)
 KERNEL_NAMES = {"se_ard": 0, "matern52": 1, "matern32": 2, "exp": 3, "host_k": 4}
 SELECT_UCB, SELECT_EI, SELECT_VAR = range(3)  # include/gpe_batch_select.h: the rules of select_batch
+REMOVE_AUTO, REMOVE_UPDATE, REMOVE_RECOMPUTE = range(3)  # include/gpe_remove.h: the `how` of remove_samples
+REMOVE_HOW = {"auto": 0, "update": 1, "recompute": 2}
 KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
@@ -113,6 +115,10 @@ def _sig(lib, prefix):
             "add_samples": [_vp, _dp, _i64, C.c_int, _dp, C.c_int],
             "append_max_chunk": [],
             "debug_append_slices": [_i64, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)],
+            # include/gpe_remove.h: samples removed by a blocked update of the factor
+            "remove_samples": [_vp, C.POINTER(_i64), _i64, _dp, C.c_int, C.c_int],
+            "remove_max_vectors": [],
+            "debug_remove_plan": [_i64, _i64, _i64, C.c_int, C.POINTER(_i64)],
             # include/gpe_sparse.h: the sparse pseudo-input GP
             "sp_create": [C.c_int, C.POINTER(_vp)],
             "sp_destroy": [_vp],
@@ -339,6 +345,22 @@ class Handle:
         assert om.shape[0] == self.N + q
         rc = self._chk(self.lib.fn("add_samples")(self._h, _d(X), q, D, _d(om), om.shape[1]), "add_samples")
         self.N += q
+        return rc
+
+    def remove_samples(self, idx, obs_mean, how="auto") -> int:
+        """gpe_remove_samples (include/gpe_remove.h; HIP library only): the samples at the indices idx (any order) leave the model;
+        obs_mean has ALL N - q remaining rows.  how: "auto", "update" (the factor update) or "recompute".  Returns the status, 0."""
+        om = np.asarray(obs_mean, dtype=np.float64)
+        if om.ndim == 1:
+            om = om[:, None]
+        om = _c(om, "F")
+        ix = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
+        q = int(ix.size)
+        assert om.shape[0] == self.N - q
+        how = REMOVE_HOW.get(how, how)
+        rc = self._chk(self.lib.fn("remove_samples")(self._h, ix.ctypes.data_as(C.POINTER(_i64)), q, _d(om), om.shape[1], int(how)),
+                       "remove_samples")
+        self.N -= q
         return rc
 
     def log_lik(self) -> float:
@@ -735,6 +757,21 @@ def device_count(lib) -> int:
 def append_max_chunk(lib) -> int:
     """gpe_append_max_chunk: rows the device tail of gpe_add_samples factorises at once."""
     return int(lib.fn("append_max_chunk")())
+
+
+def remove_max_vectors(lib) -> int:
+    """gpe_remove_max_vectors: update vectors one pass of gpe_remove_samples carries."""
+    return int(lib.fn("remove_max_vectors")())
+
+
+def debug_remove_plan(lib, n, i0, q, tail_only=False):
+    """gpe_debug_remove_plan: (path AUTO takes: 1 update / 2 recompute, passes, launches on the factor, scratch doubles) of a
+    call that removes q indices, the smallest i0, from a model of n samples.  Raises EngineError on a bad argument."""
+    out = (_i64 * 4)()
+    rc = lib.fn("debug_remove_plan")(int(n), int(i0), int(q), int(bool(tail_only)), out)
+    if rc != 0:
+        raise EngineError(f"debug_remove_plan: bad argument ({n}, {i0}, {q}, {tail_only}): status {rc}")
+    return tuple(int(v) for v in out)
 
 
 def debug_live_buffers(lib):

@@ -584,6 +584,29 @@ size_t append_scratch_doubles(int64_t n);  // scratch of launch_append_tail for 
 bool launch_append_tail(hipStream_t s, const double* Zt, const double* Qt, int64_t ldq, int q, int64_t n, const KParams& kp, double* A,
                         int64_t ld, int* info, double* scratch, int slices_cap);
 
+// ---- removal of samples by a blocked factor update (remove.hip; include/gpe_remove.h) ------------------------------
+#define GPE_RM_CAP 32   // update vectors carried per pass (gpe_remove_max_vectors)
+#define GPE_RM_PANEL 256 // columns of the old factor per rot / apply launch pair
+// the indices one pass removes from its source factor, ascending; vector k is born at column idx[k]
+struct RmList {
+    int a;
+    int idx[GPE_RM_CAP];
+};
+int remove_max_vectors();
+// scratch of one call on a factor of order n: U (n rounded up to 64, x GPE_RM_CAP), the coefficient table of one panel and the
+// kept samples' old indices (int32)
+size_t remove_u_ld(int64_t n);
+size_t remove_coef_doubles();
+// Xt[j + d ld] <- Xt[keep[j] + d ld] for j < n_new, 0 for n_new <= j < n_old, in place, every one of `rows` rows
+void launch_rm_xt(hipStream_t s, double* Xt, int64_t ld, int rows, const int* keep, int64_t n_new, int64_t n_old);
+// columns [0, ch) of the old factor (none of them removed): the kept rows move up
+void launch_rm_head(hipStream_t s, const double* src, double* dst, int64_t ld, int64_t n, int64_t ch, const RmList& R);
+// the panel of old columns [c0, min(c0 + GPE_RM_PANEL, n)): k_rm_rot on its triangle rows (reflectors into coef, finished rows to
+// dst), then k_rm_apply on every row below (none for the last panel).  first: no vector is older than this panel (U is not read).
+// Returns the number of launches
+int launch_rm_panel(hipStream_t s, const double* src, double* dst, int64_t ld, int64_t n, int64_t c0, const RmList& R, bool first, double* U,
+                    int64_t ldu, double* coef);
+
 // ---- sparse pseudo-input GP (sparse.hip; include/gpe_sparse.h) -----------------------------------------------------
 // V (M pseudo-inputs x a chunk of nc points) in either layout of the batched query: element (n, i) at Z[n sn + i si]
 int64_t sparse_default_chunk(int64_t M);             // columns of V per chunk unless GPE_SPARSE_CHUNK says otherwise

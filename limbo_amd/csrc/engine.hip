@@ -17,6 +17,7 @@
 #include "../../include/gpe.h"
 #include "../../include/gpe_joint.h"
 #include "../../include/gpe_append.h"
+#include "../../include/gpe_remove.h"
 #include "../../include/gpe_sparse.h"
 #include "../../include/gpe_sparse_grad.h"
 #include "../../include/gpe_query_grad.h"
@@ -1262,6 +1263,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 #include "select.hpp" // greedy batch selection with hallucinated observations (include/gpe_batch_select.h)
 #include "kg.hpp"     // the knowledge gradient over a finite alternative set (include/gpe_kg.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
+#include "remove.hpp" // samples removed by a blocked update of the factor (include/gpe_remove.h)
 #include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)
 #include "sparse_grad.hpp" // its analytic gradient: one more pass over the chunks (include/gpe_sparse_grad.h)
 
