@@ -18,7 +18,7 @@ static bool batch_compatible(const gpe_ctx* a, const gpe_ctx* b)
 // Device copies of the batch tables: a pool per device behind a mutex.  (They were thread_local once: every host
 // thread that ever batched — par::loop spawns fresh ones per call on a multi-GPU node — leaked 41 KB of device memory.)
 static std::mutex g_tab_mu;
-static std::vector<BatchTab*> g_tab_pool[16];
+static std::vector<BatchTab*> g_tab_pool[GPE_MAX_DEVICES];
 static BatchTab* acquire_tab(int device)
 {
     {
@@ -71,7 +71,7 @@ static int batch_enqueue_fused(gpe_ctx** cs, int Gc, BatchTab** tab_out, const B
                 return rc;
         }
     }
-    if (c0->device >= 16)
+    if (c0->device >= GPE_MAX_DEVICES)
         return GPE_ERR_UNSUPPORTED;
     bool batch_has_tail = false, batch_has_tall = false; // which data-flow launches this batch's plan issues
     { // the data-flow launches' hand-over buffers: every member's with the capacities and the armed parity of member 0's
@@ -112,7 +112,7 @@ static int batch_enqueue_fused(gpe_ctx** cs, int Gc, BatchTab** tab_out, const B
     const size_t dbl = sizeof(double);
     const unsigned long long sz[GPE_BT_CLS] = {(unsigned long long)(dbl * c0->ld * c0->cap), (unsigned long long)(dbl * c0->ld * xt_rows(c0->D)),
                                                (unsigned long long)(dbl * c0->ld * c0->P), (unsigned long long)(dbl * c0->ld * c0->P),
-                                               (unsigned long long)(dbl * (c0->cap / NB) * NB * NB), (unsigned long long)(dbl * GPE_HEAD_TILES * NB * NB), 64, 8192,
+                                               (unsigned long long)(dbl * (c0->cap / NB) * NB * NB), shell::HEAD_BYTES, shell::INFO_BYTES, shell::HSCAL_BYTES,
                                                (unsigned long long)(c0->dLinv ? dbl * c0->ld * c0->cap : 0), (unsigned long long)(c0->dKinv ? dbl * c0->ld * c0->cap : 0),
                                                (unsigned long long)(dbl * c0->dGradPartial.capacity()),
                                                (unsigned long long)(c0->dTail ? dbl * 2 * (c0->tail_cap + c0->tall_cap) : 0),
@@ -166,7 +166,7 @@ static int batch_finish_fused(gpe_ctx** cs, int Gc, int* rc, const BatchWant* wa
         c->have_L = true;
         c->inv_ok = false;
         c->al_prefilled = false;
-        c->ll_partials = c0->flow_solve && nblk <= 256 ? (int)nblk : 0;
+        c->ll_partials = c0->flow_solve && nblk <= shell::LL_MAX_BLOCKS ? (int)nblk : 0;
         // the usual finish on the handle's own (idle) stream: sums the per-block partials; a sweep that gave up
         // (never expected) is re-run block by block for that GP alone
         const int64_t retries = c->flow_retries;

@@ -5,6 +5,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "shell_layout.h" // (the regions of a handle's two shell blocks; GPE_MAX_P and k_panel256's polled buffer size with them)
 
 // ---- environment switches (SWITCHES.md); callers keep the result in a function-local static: read once per process ----
 // an integer switch: its value, or dflt when it is not set
@@ -18,7 +19,7 @@ static inline bool env_flag(const char* name, bool dflt) { return env_int(name, 
 static inline bool env_not_zero(const char* name) { return env_flag(name, true); }
 
 #define GPE_MAX_THETA 64
-#define GPE_MAX_P 8 // outputs handled per solve launch
+#define GPE_MAX_DEVICES 16 // per-device tables of the host side (shell pool, gate, live handles, batch tables) have this many entries
 
 // kernel-functor parameters, pre-digested on the host (kernel/kernel.hpp:116-123 and the
 // per-kernel set_params: squared_exp_ard.hpp:96-105, matern_five_halves.hpp:97-102)
@@ -210,7 +211,7 @@ void launch_diag(hipStream_t s, double* A, int64_t lda, int jb, double* Xt, int*
 // one fused 64-column step below the factored diagonal block at (j0, j0): L21 = A21 X^T for rows
 // j0+64 .. M-1, the updates of the next `nt` 64-column blocks of the outer panel, and (do_next) the
 // factorisation + inversion of the next diagonal block (-> Xt_next).  Full 64-blocks only.
-typedef unsigned long long gpe_epoch_t; // the value of a hand-over flag word: the serial number of the launch that set it
+typedef shell::flag_t gpe_epoch_t; // the value of a hand-over flag word: the serial number of the launch that set it
 // Hs: nt scratch tiles (64 x 64 each) for the L of the first nt row blocks; launch_head_copy moves
 // the tiles of the nf fused steps of the panel at p0 (nt0 = tiles of its first step) into A.
 // dnext / dfirst (>= 0 to enable): see k_panel_step — pieces of the next outer panel's first diagonal block
@@ -274,13 +275,9 @@ bool launch_ragged_update(hipStream_t s, double* C, int64_t ldc, const double* A
                           double* scratch, int64_t scratch_doubles); // potrf_tail.hip: a ragged order's last block behind k_tail
 void launch_tail(hipStream_t s, double* A, int64_t lda, int64_t t0, int64_t t1, int64_t N64, int64_t M, double* Xt_all, int* info,
                  double* buf_cur, double* buf_next, const TailGen* gen = nullptr);
-// S22 / S22_next: the polled hand-over buffers (block inverses + head tiles), 33,792 doubles each, holding the all-ones
-// pattern when the launch starts (the launch arms S22_next)
-#define GPE_S22_TILE 20 // the two buffers sit in tiles 20..28 of either half of gpe_ctx::dHead
-#define GPE_S22_TILES 9
-// the device block behind gpe_ctx::dHead: 32 + 32 head tiles (by panel parity), the scratch sum of the next diagonal
-// block, and one tile's worth of hand-over flag words (hflag: one unsigned per head tile, same indexing as the tiles)
-#define GPE_HEAD_TILES 66
+// S22 / S22_next: the polled hand-over buffers (block inverses + head tiles), P256_POLLED_DOUBLES each, holding the all-ones
+// pattern when the launch starts (the launch arms S22_next); they are shell::s22 of either half of the head block, and Dacc
+// and hflag of the panel launches shell::diag_sum and shell::hflags (shell_layout.h)
 void launch_head_copy(hipStream_t s, double* A, int64_t lda, int64_t p0, int nt0, int nf, const double* H);
 // inverses of diagonal blocks b0 .. b0+nblocks-1 of an existing factor L (order N) into
 // Xt_all + 4096 b

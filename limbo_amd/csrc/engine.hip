@@ -94,8 +94,7 @@ void gpe_trace_add(const char* name, hipStream_t s, hipEvent_t e0, hipEvent_t e1
 
 #define NB 64
 #define NBO 256 // outer panel width of the two-level blocked algorithms: four blocks of NB
-// pinned staging of the small path: results in [0, 256), inputs (obs_mean: (n + 1) x P <= 257 x 3; query points: 8 x 64) from 256 on
-#define SMALL_STAGE_DOUBLES (256 + 1024)
+static_assert(NB == shell::EDGE && NBO == shell::PANEL, "shell_layout.h counts in these tiles and panels");
 
 namespace {
 
@@ -107,15 +106,69 @@ struct PhaseRec {
 
 } // namespace
 
+// events of a handle: a vector that destroys what it holds (get_event, nth_event and Marks take it as the vector it is) ...
+struct DEVBUF_LOCAL Events : std::vector<hipEvent_t> {
+    Events() = default;
+    Events(Events&&) = delete; // (neither moved nor copied)
+    ~Events() { std::for_each(begin(), end(), hipEventDestroy); }
+};
+struct DEVBUF_LOCAL Event { // ... and a single one, created by the site that first needs it
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&&) = delete;
+    ~Event() { (void)(e && hipEventDestroy(e)); }
+    operator hipEvent_t() const { return e; }
+};
+
+// The shell of a handle, what survives it: the two streams, the device block and the coherent pinned block of shell_layout.h.
+// Move-only; the destructor releases.  gpe_destroy hands it to a pool per device and the next gpe_create there takes it out
+// (ShellPool, below).  Not a DevBuf: a pooled shell outlives its handle, gpe_debug_live_buffers counts what a handle owns.
+class DEVBUF_LOCAL Shell {
+    struct Parts {
+        hipStream_t main = nullptr, bulk = nullptr; // main: highest priority, the critical path (create_main_stream)
+        double* dev = nullptr;
+        char* pin = nullptr;
+    } p_;
+
+public:
+    Shell() = default;
+    Shell(Shell&& o) noexcept { std::swap(p_, o.p_); }
+    Shell& operator=(Shell&& o) noexcept { return std::swap(p_, o.p_), *this; } // (what this held leaves with o)
+    ~Shell() { reset(); }
+    hipError_t create(); // on the current device; on failure the shell is empty
+    void reset();        // nothing of it may be in flight
+    explicit operator bool() const { return p_.pin != nullptr; }
+
+    hipStream_t stream() const { return p_.main; }
+    hipStream_t stream2() const { return p_.bulk; }
+    double* scal() const { return p_.dev; }
+    double* head() const { return shell::head(p_.dev); }
+    double* head_half(int parity) const { return shell::head_half(p_.dev, parity); }
+    double* s22(int parity) const { return shell::s22(p_.dev, parity); }
+    double* diag_sum() const { return shell::diag_sum(p_.dev); }
+    gpe_epoch_t* hflags(int parity) const { return shell::hflags(p_.dev, parity); }
+    char* pinned() const { return p_.pin; }
+    int* info() const { return shell::info(p_.pin); }
+    unsigned long long* seq() const { return shell::seq(p_.pin); }
+    double* hscal() const { return shell::hscal(p_.pin); }
+    double* ll_partials() const { return shell::ll_partials(p_.pin); }
+    double* small() const { return shell::small(p_.pin); }
+    double* small_kta() const { return shell::small_kta(p_.pin); }
+    double* small_var() const { return shell::small_var(p_.pin); }
+    double* small_in() const { return shell::small_in(p_.pin); }
+};
+
 struct gpe_ctx {
     DEVBUF_LOCAL ~gpe_ctx() = default; // (frees what free_dev has not; not an exported symbol)
     std::atomic<uint64_t> epoch{1}; // bumped by every call that can change what a query answers (gpe_epoch: round 6 — the C++ drop-in's
                                     // per-device query replicas are valid exactly as long as this has not moved)
     int device = 0;  // physical HIP device
     int ldevice = 0; // the device id the caller used (differs from `device` only under GPE_VIRTUAL_DEVICES)
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;      // look-ahead: bulk of a trailing update runs here, behind the next panel
-    std::vector<hipEvent_t> la_events; // untimed events ordering the two streams
+    Shell shell; // the streams, the device block and the pinned block (shell_layout.h); the members marked "shell view" below are
+                 // pointers into it, set by view_shell and by nothing else
+    hipStream_t stream = nullptr;  // shell view
+    hipStream_t stream2 = nullptr; // shell view.  Look-ahead: bulk of a trailing update runs here, behind the next panel
+    Events la_events;              // untimed events ordering the two streams
     int64_t tail_max = 2816;           // the last <= this many columns by one launch (k_tail; GPE_TAIL_MAX=0: by panels to the end);
                                        // 2816 against 2560: the one update in front of it has 253 tiles instead of 230 for the 256 CUs
                                        // (0.64 against 0.57 of the fp64 peak), profiles/r04_tail_max_sizes.log
@@ -138,7 +191,7 @@ struct gpe_ctx {
     int64_t tail_lay = -1, tall_lay = -1; // nt * 65536 + nb of the pair's previous launch (-1: both buffers entirely all-ones)
     bool gen_mode = false; // this evaluation: the one launch that is the whole factorisation generates K (compute_enqueue)
     unsigned p256_count = 0;           // launches of k_panel256 so far: its polled X22 copies alternate between two buffers
-    std::vector<hipEvent_t> pl_events; // ... one per outer panel: the one-launch panel is complete (early release of the look-ahead stream)
+    Events pl_events;                  // ... one per outer panel: the one-launch panel is complete (early release of the look-ahead stream)
     bool stop_events = true;    // next-panel update signals through its own dispatch (hipExtLaunchKernel stop event)
     bool fuse_diag = true;      // next diagonal block factored inside the next-panel update launch (k_upd_fused)
     bool lookahead = true;             // GPE_LOOKAHEAD=0 disables
@@ -156,7 +209,7 @@ struct gpe_ctx {
     double* dGrad = nullptr;                  // view: the last gradient, inside dGradPartial
     DevBuf<double> dLooS, dLooV; // leave-one-out scratch: N x N and N x (P + 2) (+8)
     DevBuf<double> dQuery; // query scratch kept between calls while it is small (single-point queries: no malloc/free)
-    double* dHead = nullptr; // view: scratch tiles of the fused panel steps (k_panel_step), inside dScal's block
+    double* dHead = nullptr; // shell view: the head block (the batch table's base of it; its regions go by shell.head_half(), s22(), ...)
     bool panel_handover = true; // head tiles of a panel step change hands (potrf_panel.hip); GPE_PANEL_HANDOVER=0: re-derived
     bool panel_handover_cfg = true; // what the caller / environment chose: a hand-over timeout switches panel_handover off
     int handover_off_left = 0;      // ... for this many evaluations only, then it is re-armed (one hiccup is not forever)
@@ -170,22 +223,21 @@ struct gpe_ctx {
     Inv2Plan* inv2 = nullptr; // ... and its plan, rebuilt when N, ld or a buffer changes
     int64_t inv_pad_n = -1;           // U and the T-form / W buffer read as zero beyond the inv_pad_n x inv_pad_n part (-1: unknown)
     Inv2Plan* inv2_batched = nullptr; // ... the plan of a batched sequence of >= 4 members led by this handle (no chunked k ranges)
-    hipEvent_t chain_ev = nullptr; // the end of this handle's last evaluation chain when that ran on a CU-masked stream (ChainScope) ...
+    Event chain_ev;                // the end of this handle's last evaluation chain when that ran on a CU-masked stream (ChainScope) ...
     bool chain_pending = false;    // ... and nobody has waited for it yet: the HOST does (wait_chain), never the handle's own stream
     bool inv_early = false;   // set by gpe_hp_objective around compute_enqueue: start K^-1's lowest level beside the sweep
     bool inv_prefix_done = false; // ... done on stream2 for the factor at hand; inv_ev completes behind it
-    hipEvent_t inv_ev = nullptr, inv_ev0 = nullptr;
-    int* dInfo = nullptr; // view: = hInfo, pinned host memory the kernels write directly (no copy-back, no device memset)
-    double* dScal = nullptr; // the HandleShell's device block (gpe_create / gpe_destroy): [0] sum log L_ii, [1] trace(om^T alpha), [2] knn scratch, [8 .. 8 + 2 nblk) per-block partials
+    Event inv_ev, inv_ev0;
+    int* dInfo = nullptr; // shell view: = hInfo, pinned host memory the kernels write directly (no copy-back, no device memset)
+    double* dScal = nullptr; // shell view: the device block's scalars, [SCAL_LOGDET] sum log L_ii, [SCAL_TRACE] trace(om^T alpha), [SCAL_KNN] k_knn's scratch
     int ll_partials = 0;     // > 0: the backward sweep left that many per-block partial sums instead of [0], [1]
     bool al_prefilled = false; // alpha holds the sentinel pattern of the data-flow sweep
-    int* hInfo = nullptr;    // view: hPinned + 0
-    double* hScal = nullptr; // view: hPinned + 128
+    int* hInfo = nullptr;    // shell view: the info words
+    double* hScal = nullptr; // shell view: [0], [1] the log-likelihood terms; the sweep's per-block partials are shell.ll_partials()
     bool have_L = false, inv_ok = false, host_K = false, ll_ok = false;
     // one-launch small-N path (small.hip): pinned staging the kernels read / write directly, the word the host spins on
-    char* hPinned = nullptr;             // the HandleShell's pinned allocation behind hInfo / hSmallSeq / hScal / hSmall
-    double* hSmall = nullptr;            // view: hScal + 1024.  [0..2): log-lik terms | [16 .. 16+8*GPE_MAX_P+8): kta, var | [256..): obs_mean / query points in
-    unsigned long long* hSmallSeq = nullptr; // view: hPinned + 64.  8 sequence words (one per query point; word 0 for add_sample)
+    double* hSmall = nullptr;            // shell view: [0, 2) log-lik terms; shell.small_kta(), small_var() results, small_in() obs_mean / query points in
+    unsigned long long* hSmallSeq = nullptr; // shell view: the sequence words (one per query point; word 0 for add_sample)
     unsigned long long small_seq = 0;
     bool small_path = true;              // GPE_SMALL=0 disables
     int64_t small_calls = 0;             // calls served by the small path (instrumentation / tests)
@@ -200,10 +252,18 @@ struct gpe_ctx {
     // instrumentation
     bool prof = false;
     std::vector<PhaseRec> pending;
-    std::vector<hipEvent_t> pool;
+    Events pool;
     double ph_ms[GPE_PH_COUNT] = {0}, ph_flops[GPE_PH_COUNT] = {0};
     int64_t ph_launches[GPE_PH_COUNT] = {0};
     std::string err;
+
+    void view_shell()
+    {
+        stream = shell.stream(), stream2 = shell.stream2();
+        dScal = shell.scal(), dHead = shell.head();
+        hInfo = dInfo = shell.info(); // mapped pinned memory: same address on the device (unified addressing)
+        hSmallSeq = shell.seq(), hScal = shell.hscal(), hSmall = shell.small();
+    }
 };
 
 namespace {
@@ -553,14 +613,31 @@ struct DevGuard {
 };
 
 
-// what survives a handle: see gpe_create
-struct HandleShell {
-    hipStream_t stream, stream2;
-    double* dScal;
-    char* hPinned;
+// Shells of destroyed handles, per device, last in first out: limbo creates and drops GPs freely (value semantics, one clone per
+// hyper-parameter fit and thread — kernel_lf_opt.hpp:79), and creating two streams and a pinned allocation costs milliseconds.
+// The pool is never destructed (leaked on purpose): a pooled shell is not released when the process ends, because hipFree and
+// hipStreamDestroy during static destruction would run after the HIP runtime may be gone.
+struct ShellPool {
+    std::mutex mu;
+    std::vector<Shell> free[GPE_MAX_DEVICES];
 };
-std::mutex g_shell_mu;
-std::vector<HandleShell> g_shells[16];
+ShellPool& g_shells = *new ShellPool;
+Shell shell_pool_take(int device) // an empty shell: nothing pooled for this device
+{
+    Shell sh;
+    std::lock_guard<std::mutex> lk(g_shells.mu);
+    if (device < GPE_MAX_DEVICES && !g_shells.free[device].empty()) {
+        sh = std::move(g_shells.free[device].back());
+        g_shells.free[device].pop_back();
+    }
+    return sh;
+}
+void shell_pool_put(int device, Shell sh) // a shell that is not kept (64 pooled already) releases itself on the way out
+{
+    std::lock_guard<std::mutex> lk(g_shells.mu);
+    if (device < GPE_MAX_DEVICES && g_shells.free[device].size() < 64)
+        g_shells.free[device].push_back(std::move(sh));
+}
 
 // Devices as the callers count them.  GPE_VIRTUAL_DEVICES=n (tests): n logical devices dealt round-robin over the
 // physical ones, so that the multi-device placement of the C++ policies (clones of one GP on several devices,
@@ -582,6 +659,36 @@ int logical_devices()
 }
 
 } // namespace
+
+// One device block and one coherent (fine-grained) pinned block — the small path's host side reads the pinned words while the
+// stream is still busy.  The hand-over flag words start from zero, in the order of the stream the panel steps run on.
+hipError_t Shell::create()
+{
+    hipError_t e;
+    if ((e = create_main_stream(&p_.main)) != hipSuccess || (e = create_bulk_stream(&p_.bulk)) != hipSuccess
+        || (e = hipMalloc(&p_.dev, shell::DEV_BYTES)) != hipSuccess
+        || (e = hipMemsetAsync(shell::flag_tile(p_.dev), 0, sizeof(double) * shell::TILE, p_.main)) != hipSuccess
+        || (e = hipHostMalloc(&p_.pin, shell::PINNED_BYTES, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess) {
+        if (p_.main)
+            hipStreamSynchronize(p_.main); // (the memset, if it got that far)
+        reset();
+    }
+    return e;
+}
+void Shell::reset()
+{
+    if (p_.dev)
+        hipFree(p_.dev);
+    if (p_.pin)
+        hipHostFree(p_.pin);
+    for (hipStream_t s : {p_.bulk, p_.main})
+        if (s)
+            flow_gate_forget(s); // (a stream is about to be destroyed: partitions.hpp)
+    for (hipStream_t s : {p_.bulk, p_.main})
+        if (s)
+            hipStreamDestroy(s);
+    p_ = Parts{};
+}
 
 // =============================================================================================
 // C-ABI
@@ -606,52 +713,18 @@ int gpe_create(int device_id, gpe_handle* out)
         delete c;
         return GPE_ERR_HIP;
     }
-    // Streams, the scratch block and the pinned block of a destroyed handle are kept for the next one on that device
-    // (limbo creates and drops GPs freely: value semantics, one clone per hyper-parameter fit and thread —
-    // kernel_lf_opt.hpp:79; creating two streams and a pinned allocation costs milliseconds).
-    bool reused = false;
-    if (c->device < 16) {
-        std::lock_guard<std::mutex> lk(g_shell_mu);
-        auto& pool = g_shells[c->device];
-        if (!pool.empty()) {
-            const HandleShell sh = pool.back();
-            pool.pop_back();
-            c->stream = sh.stream;
-            c->stream2 = sh.stream2;
-            c->dScal = sh.dScal;
-            c->hPinned = sh.hPinned;
-            reused = true;
-        }
-    }
-    if (!reused
-        && (create_main_stream(&c->stream) != hipSuccess || create_bulk_stream(&c->stream2) != hipSuccess
-            // one device block [dScal 8 KiB | dHead GPE_HEAD_TILES tiles] and one coherent (fine-grained) pinned block
-            // [hInfo 64 B | hSmallSeq 64 B | hScal 8 KiB | hSmall]: the small path's host side reads the pinned words while
-            // the stream is still busy
-            || hipMalloc(&c->dScal, 8192 + sizeof(double) * GPE_HEAD_TILES * NB * NB) != hipSuccess
-            // the hand-over flag words start from zero, in the order of the stream the panel steps run on
-            || hipMemsetAsync(c->dScal + 1024 + 65 * NB * NB, 0, sizeof(double) * NB * NB, c->stream) != hipSuccess
-            || hipHostMalloc(&c->hPinned, 128 + 8192 + sizeof(double) * SMALL_STAGE_DOUBLES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)) {
-        if (c->stream)
-            hipStreamSynchronize(c->stream); // (the memset, if it got that far)
-        if (c->hPinned)
-            hipHostFree(c->hPinned);
-        if (c->dScal)
-            hipFree(c->dScal);
-        if (c->stream2)
-            hipStreamDestroy(c->stream2);
-        if (c->stream)
-            hipStreamDestroy(c->stream);
+    c->shell = shell_pool_take(c->device); // a destroyed handle's, where one is kept for this device
+    if (!c->shell && c->shell.create() != hipSuccess) {
         delete c;
         return GPE_ERR_HIP;
     }
-    c->dHead = c->dScal + 1024;
+    c->view_shell();
     {
         // the CU-masked stream pairs of the chain partitions (ChainScope) are created when a device has TWO live handles for the
         // first time: creating them takes tens of milliseconds, which must not fall into the first evaluation that meets another
         // one.  (the count is of LIVE handles — gpe_destroy takes its handle off it again.)  The first live handle
         // also shows the process in the GPU's users file (other processes then take turns with it, xproc_enter).
-        if (c->device < 16) {
+        if (c->device < GPE_MAX_DEVICES) {
             const int now_live = g_live[c->device].fetch_add(1) + 1;
             GateDev& gd = gate_dev();
             std::lock_guard<std::recursive_mutex> lk(gd.mu);
@@ -662,15 +735,10 @@ int gpe_create(int device_id, gpe_handle* out)
         }
     }
     // the polled X22 copies of k_panel256 (both buffers: a block from the pool may have been left in either state)
-    hipMemsetAsync(c->dHead + GPE_S22_TILE * (NB * NB), 0xFF, sizeof(double) * GPE_S22_TILES * NB * NB, c->stream);
-    hipMemsetAsync(c->dHead + (32 + GPE_S22_TILE) * (NB * NB), 0xFF, sizeof(double) * GPE_S22_TILES * NB * NB, c->stream);
-    c->hInfo = (int*)c->hPinned;
-    c->hSmallSeq = (unsigned long long*)(c->hPinned + 64);
-    c->hScal = (double*)(c->hPinned + 128);
-    c->hSmall = c->hScal + 1024;
-    memset(c->hPinned, 0, 128);
+    for (int parity = 0; parity < 2; ++parity)
+        hipMemsetAsync(c->shell.s22(parity), 0xFF, sizeof(double) * shell::S22_TILES * shell::TILE, c->stream);
+    memset(c->shell.pinned(), 0, shell::HSCAL_OFF); // the info and the sequence words
     c->small_path = env_flag("GPE_SMALL", c->small_path);
-    c->dInfo = c->hInfo; // mapped pinned memory: same address on the device (unified addressing)
     c->panel_handover = env_flag("GPE_PANEL_HANDOVER", c->panel_handover);
     c->panel_handover_cfg = c->panel_handover;
     c->fuse_diag = env_flag("GPE_FUSE_DIAG", c->fuse_diag);
@@ -702,42 +770,13 @@ int gpe_destroy(gpe_handle c)
         gpe_destroy(c->joint);
         c->joint = nullptr;
     }
-    if (c->inv_ev) {
-        hipEventDestroy(c->inv_ev);
-        hipEventDestroy(c->inv_ev0);
-    }
-    if (c->chain_ev) {
-        (void)wait_chain(c);
-        hipEventDestroy(c->chain_ev);
-    }
+    (void)wait_chain(c);
     drain_phases(c);
-    for (auto e : c->pool)
-        hipEventDestroy(e);
     free_dev(c);
     c->dTail.reset();
-    for (auto e : c->pl_events)
-        hipEventDestroy(e);
-    for (auto e : c->la_events)
-        hipEventDestroy(e);
     hipStreamSynchronize(c->stream2);
-    bool kept = false;
-    if (c->device < 16) {
-        std::lock_guard<std::mutex> lk(g_shell_mu);
-        auto& pool = g_shells[c->device];
-        if (pool.size() < 64) {
-            pool.push_back(HandleShell{c->stream, c->stream2, c->dScal, c->hPinned});
-            kept = true;
-        }
-    }
-    if (!kept) {
-        hipFree(c->dScal);
-        hipHostFree(c->hPinned);
-        flow_gate_forget(c->stream2);
-        flow_gate_forget(c->stream);
-        hipStreamDestroy(c->stream2);
-        hipStreamDestroy(c->stream);
-    }
-    if (c->device < 16 && g_live[c->device].fetch_sub(1) == 1) { // the process's last handle on this GPU: nothing of it can be in flight
+    shell_pool_put(c->device, std::move(c->shell)); // (the handle's events go with the handle, below)
+    if (c->device < GPE_MAX_DEVICES && g_live[c->device].fetch_sub(1) == 1) { // the process's last handle on this GPU: nothing of it can be in flight
         GateDev& gd = gate_dev();
         std::lock_guard<std::recursive_mutex> lk(gd.mu);
         if (g_live[c->device].load() == 0)
@@ -867,15 +906,15 @@ int gpe_update_alpha(gpe_handle c, const double* obs_mean)
         return GPE_ERR_STATE;
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
-    if (c->small_path && c->N <= small_max_n() && c->P <= 4 && (int64_t)c->N * c->P <= 1024) {
+    if (c->small_path && c->N <= small_max_n() && c->P <= 4 && (int64_t)c->N * c->P <= shell::SMALL_IN_DOUBLES) {
         // one launch, no copies (small.hip): obs_mean read from pinned memory (or the device copy when none is given)
         SmallAlphaArgs a{};
         a.L = c->dA;
         a.ld = c->ld;
         a.Xinv = c->dXinv;
         if (obs_mean) {
-            memcpy(c->hSmall + 256, obs_mean, sizeof(double) * (size_t)(c->N * c->P));
-            a.om_src = c->hSmall + 256;
+            memcpy(c->shell.small_in(), obs_mean, sizeof(double) * (size_t)(c->N * c->P));
+            a.om_src = c->shell.small_in();
             a.ldom = c->N;
             a.Om = c->dOm;
         }
@@ -964,9 +1003,10 @@ static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* o
     if (ldo <= 0)
         ldo = n + 1;
     digest_kernel(c);
-    if (c->small_path && n >= 1 && n <= small_max_n() && P <= 3 && c->have_L) {
-        // one launch, no copies (small.hip): x travels as a kernel argument, obs_mean is read from pinned memory
-        double* om_stage = c->hSmall + 256;
+    if (c->small_path && n >= 1 && n <= small_max_n() && P <= shell::SMALL_ADD_MAX_P && c->have_L) {
+        // one launch, no copies (small.hip): x travels as a kernel argument, obs_mean is read from pinned memory ((n + 1) x P
+        // doubles: inside the staging region for every n and P that get here, shell_layout.h)
+        double* om_stage = c->shell.small_in();
         for (int p = 0; p < P; ++p)
             memcpy(om_stage + (int64_t)p * (n + 1), obs_mean + (int64_t)p * ldo, sizeof(double) * (size_t)(n + 1));
         c->hInfo[0] = c->hInfo[1] = 0;
@@ -1011,7 +1051,7 @@ static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* o
     c->hInfo[0] = c->hInfo[1] = 0; // nothing of this handle is in flight here
     // k(x_i, x_new) for i = 0..n (gp.hpp:583-586), no noise yet
     launch_build_Ks(s, c->dXt, ld, n + 1, c->dXt + n, ld, 1, c->kp, c->dW, ld);
-    GPE_LAUNCH(k_knn, dim3(1), dim3(1), 0, s, c->dW.get(), n, c->kp.diag_add, c->dScal + 2);
+    GPE_LAUNCH(k_knn, dim3(1), dim3(1), 0, s, c->dW.get(), n, c->kp.diag_add, &c->dScal[shell::SCAL_KNN]);
     auto new_row = [c, s, n, ld] {
         PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)n * n);
         if (n > 0) {
@@ -1023,7 +1063,7 @@ static int add_sample_locked(gpe_ctx* c, const double* x, int D, const double* o
             GPE_LAUNCH(k_vec_to_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c->dY.get(), c->dA + n, ld,
                                n);
         }
-        launch_append_diag(s, c->dA + n, ld, n, c->dScal + 2, c->dInfo); // gp.hpp:596-597
+        launch_append_diag(s, c->dA + n, ld, n, &c->dScal[shell::SCAL_KNN], c->dInfo); // gp.hpp:596-597
         launch_diag_inv(s, c->dA, ld, n + 1, n / NB, 1, c->dXinv); // the last block gained a row
     };
     new_row();

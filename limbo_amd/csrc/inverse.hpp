@@ -49,8 +49,8 @@ static void inv2_start_early(gpe_ctx* c)
     if (!c->inv_early || c->prof || g_batch.bt || !c->stream2 || !inv2_supported(c->N) || inv2_prepare(c) != GPE_OK)
         return;
     if (!c->inv_ev) {
-        hipEventCreateWithFlags(&c->inv_ev, hipEventDisableTiming);
-        hipEventCreateWithFlags(&c->inv_ev0, hipEventDisableTiming);
+        hipEventCreateWithFlags(&c->inv_ev.e, hipEventDisableTiming);
+        hipEventCreateWithFlags(&c->inv_ev0.e, hipEventDisableTiming);
     }
     hipEventRecord(c->inv_ev0, c->stream); // the factor is final
     hipStreamWaitEvent(c->stream2, c->inv_ev0, 0);
@@ -114,14 +114,7 @@ int ensure_inv(gpe_ctx* c)
     const bool overlap = !g_batch.bt && !c->prof && c->stop_events && npan >= 4;
     if (overlap)
         HIPCHK(c, c->dXp.reserve((size_t)(npan * nbo * nbo)));
-    auto ev = [&](size_t i) {
-        while (c->la_events.size() <= i) {
-            hipEvent_t e;
-            hipEventCreateWithFlags(&e, hipEventDisableTiming);
-            c->la_events.push_back(e);
-        }
-        return c->la_events[i];
-    };
+    auto ev = [&](size_t i) { return nth_event(c->la_events, i); };
     {
         PhaseScope ps(c, GPE_PH_INV, 0.0);
         // (a kernel: it takes part in batched launches, dev.h).  With the overlap only the second stream's rank-k updates

@@ -37,8 +37,8 @@ struct GateDev {
     std::chrono::steady_clock::time_point xp_attach{};
     bool xp_crowded_at_attach = false;
 };
-GateDev g_gate[16];
-std::atomic<int> g_live[16]; // live handles per physical device (gpe_create / gpe_destroy)
+GateDev g_gate[GPE_MAX_DEVICES];
+std::atomic<int> g_live[GPE_MAX_DEVICES]; // live handles per physical device (gpe_create / gpe_destroy)
 std::atomic<long long> g_xproc_waits{0}; // data-flow scopes that ran under the inter-process lock (gpe_xproc_waits)
 bool gate_on()
 {
@@ -49,7 +49,8 @@ GateDev& gate_dev()
 {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return g_gate[dev & 15];
+    static_assert((GPE_MAX_DEVICES & (GPE_MAX_DEVICES - 1)) == 0, "a power of two: the mask below");
+    return g_gate[dev & (GPE_MAX_DEVICES - 1)];
 }
 } // namespace
 namespace {
@@ -419,8 +420,8 @@ ChainScope::~ChainScope()
         // hardware queues than the chip maps at a time — measured with GPU_MAX_HW_QUEUES=8, torch in the process and eight
         // threads: masked chains got no service for seconds, their bounded polls fired (3 evaluations/s, re-runs); with the
         // own streams at the default priority, or with this, 950 evaluations/s.
-        if (!c->chain_ev && hipEventCreateWithFlags(&c->chain_ev, hipEventDisableTiming) != hipSuccess)
-            c->chain_ev = nullptr;
+        if (!c->chain_ev && hipEventCreateWithFlags(&c->chain_ev.e, hipEventDisableTiming) != hipSuccess)
+            c->chain_ev.e = nullptr;
         if (c->chain_ev && hipEventRecord(c->chain_ev, P) == hipSuccess)
             c->chain_pending = true;
         else

@@ -440,8 +440,8 @@ __global__ __launch_bounds__(512) void k_panel_step_b(double* __restrict__ A, in
 // head tile h = P256_H(s, t): the tile of strip t at step s (t = s..2), six per panel
 #define P256_H(s, t) ((s) == 0 ? (t) : ((s) == 1 ? 2 + (t) : 5))
 
-#define P256_POLLED_S (9 * 1024)                          // X11 | L21 | X22 of three diagonal blocks
-#define P256_POLLED_DOUBLES (P256_POLLED_S + 6 * NB * NB) // ... and six head tiles: 33,792 doubles per buffer
+// (P256_POLLED_S, P256_POLLED_DOUBLES: shell_layout.h, beside the tiles that hold the two buffers)
+static_assert(NB == shell::EDGE, "the shell's tiles are this file's");
 
 // The strip that factors next solves against the block inverse in the half-block form, in two phases: three quarters of its
 // solve and half of its one update run while the previous strip is still factoring (X11 and L21 of that block leave it half-way

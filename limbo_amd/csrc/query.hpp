@@ -376,10 +376,10 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
     PhaseDrain pd(c);
     const int64_t N = c->N, ld = c->ld;
     const int D = c->D, P = c->P;
-    if (c->small_path && Xq && N <= small_max_n() && M <= 8 && (int64_t)M * D <= 1024 && P <= GPE_MAX_P) {
+    if (c->small_path && Xq && N <= small_max_n() && M <= shell::SMALL_POINTS && (int64_t)M * D <= shell::SMALL_IN_DOUBLES && P <= GPE_MAX_P) {
         // the per-point query of an acquisition functor on a small GP: one launch (one workgroup per point), the
         // points read from and the results written to pinned host memory (small.hip)
-        memcpy(c->hSmall + 256, Xq, sizeof(double) * (size_t)(M * D));
+        memcpy(c->shell.small_in(), Xq, sizeof(double) * (size_t)(M * D));
         SmallQueryArgs q{};
         q.L = c->dA;
         q.ld = ld;
@@ -391,9 +391,9 @@ static int query_impl(gpe_ctx* c, const double* Xq, const double* KsHost, int64_
         q.n = (int)N;
         q.M = (int)M;
         q.D = D;
-        q.xq_host = c->hSmall + 256;
-        q.kta_host = c->hSmall + 16;
-        q.var_host = c->hSmall + 16 + 8 * GPE_MAX_P;
+        q.xq_host = c->shell.small_in();
+        q.kta_host = c->shell.small_kta();
+        q.var_host = c->shell.small_var();
         q.seq = c->hSmallSeq;
         q.seq_val = ++c->small_seq;
         q.want_kta = kta ? 1 : 0;

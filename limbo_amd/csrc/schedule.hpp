@@ -208,7 +208,8 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
     // head-tile scratch, two halves by panel parity: the copy into A is off the critical path
     // (nothing before the end of the factorisation reads those tiles of A) and may still be
     // pending on the second stream while the next panel is factored
-    double* const Hbase = c->dHead + ((p0 / NBO) & 1) * (32 * NB * NB);
+    const int parity = (int)((p0 / NBO) & 1);
+    double* const Hbase = c->shell.head_half(parity);
     // Will the trailing update of this panel be the fused launch that also factors the next panel's first
     // diagonal block (k_upd_fused)?  Then the steps of this panel pre-apply their pieces of that block.
     const bool fuse_diag = c->lookahead && !c->prof && std::min<int64_t>(pe + NBO, N) < N && c->fuse_panel && c->fuse_diag
@@ -234,9 +235,8 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             launch_diag(s, A + p0 + p0 * ld, ld, NB, Xt, c->dInfo, p0, 1);
         }
         PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)(M - p0 - NB) * NB * NB * 2.5 * 4);
-        launch_panel256(s, A, ld, p0, M, Xt, c->dInfo, fuse_diag ? pe : -1, c->dHead + 64 * NB * NB,
-                        c->dHead + ((c->p256_count & 1) * 32 + GPE_S22_TILE) * (NB * NB),
-                        c->dHead + (((c->p256_count + 1) & 1) * 32 + GPE_S22_TILE) * (NB * NB), p_done);
+        launch_panel256(s, A, ld, p0, M, Xt, c->dInfo, fuse_diag ? pe : -1, c->shell.diag_sum(), c->shell.s22(c->p256_count & 1),
+                        c->shell.s22((c->p256_count + 1) & 1), p_done);
         ++c->p256_count;
     }
     for (int64_t j0 = p0; j0 < pe && !p256; j0 += NB) {
@@ -245,7 +245,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
         double* Xt = c->dXinv + (j0 / NB) * (NB * NB);
         // fused step (k_panel_step): full 64-column blocks up to the end of the panel
         const int nt = (int)((pe - r0) / NB);
-        const bool fuse = c->fuse_panel && jb == NB && (pe - r0) % NB == 0 && r0 < M && htile + nt <= 32;
+        const bool fuse = c->fuse_panel && jb == NB && (pe - r0) % NB == 0 && r0 < M && htile + nt <= shell::STEP_HEAD_TILES;
         if (!diag_done) {
             PhaseScope ps(c, GPE_PH_POTRF_PANEL, (double)jb * jb * jb);
             launch_diag(s, A + j0 + j0 * ld, ld, jb, Xt, c->dInfo, j0, fuse ? 1 : 0);
@@ -261,8 +261,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
             const bool pre = fuse_diag && j0 > p0;
             launch_panel_step(s, A, ld, j0, M, nt, Xt, Xt + NB * NB, nt > 0 ? 1 : 0, c->dInfo, Hbase + htile * NB * NB,
                               pre ? pe : -1, pre && j0 == p0 + 2 * NB ? p0 : -1, j0 == p0 + NB ? 1 : 0,
-                              c->dHead + 64 * NB * NB,
-                              c->panel_handover ? (gpe_epoch_t*)(c->dHead + 65 * NB * NB) + ((p0 / NBO) & 1) * 32 + htile : nullptr);
+                              c->shell.diag_sum(), c->panel_handover ? c->shell.hflags(parity) + htile : nullptr);
             htile += nt;
             if (nt > 0)
                 ++nf;
@@ -327,7 +326,7 @@ static void potrf_panel(gpe_ctx* c, double* A, int64_t N, int64_t M, int64_t p0,
                 GemmArgs g = tri_update(A, ld, M, pe, pe, pe2, p0, pe);
                 g.stop_event = ev(3 * kp);
                 launch_upd_fused(s, g, A, ld, pe, pe, c->dXinv + (pe / NB) * (NB * NB), c->dInfo,
-                                 c->dHead + 64 * NB * NB); // the steps summed the pieces: no products here
+                                 c->shell.diag_sum()); // the steps summed the pieces: no products here
                 cy.next_diag_done = true;
             }
             else if (c->stop_events)
@@ -535,16 +534,16 @@ void solve_alpha(gpe_ctx* c)
     c->ll_partials = 0;
     PhaseScope ps(c, GPE_PH_SOLVE, 2.0 * (double)c->N * c->N * c->P);
     const int64_t nblk = (c->N + NB - 1) / NB;
-    const bool flow = c->flow_solve && nblk <= 256; // one data-flow launch per sweep instead of one launch per block
+    const bool flow = c->flow_solve && nblk <= shell::LL_MAX_BLOCKS; // one data-flow launch per sweep instead of one launch per block
     for (int p0 = 0; p0 < c->P; p0 += GPE_MAX_P) {
         int pc = std::min(GPE_MAX_P, c->P - p0);
         const double* om = c->dOm + (int64_t)p0 * c->ld;
         double* al = c->dAl + (int64_t)p0 * c->ld;
         if (flow) {
             launch_trsv_fwd_flow(s, c->dA, c->ld, c->N, c->dXinv, om, c->ld, c->dY, c->ld, pc, c->dInfo + 1);
-            if (!(c->P == 1 && bwd_chain_sweep(c, s, c->dY, 1, al, 0, om, c->hScal + 8)))
+            if (!(c->P == 1 && bwd_chain_sweep(c, s, c->dY, 1, al, 0, om, c->shell.ll_partials())))
                 launch_trsv_bwd_flow(s, c->dA, c->ld, c->N, c->dXinv, c->dY, 1, c->ld, al, c->ld, pc, c->dInfo + 1, 0, om, c->ld,
-                                     c->hScal + 8, p0 > 0 ? 1 : 0);
+                                     c->shell.ll_partials(), p0 > 0 ? 1 : 0);
             continue;
         }
         launch_copy2d(s, om, c->ld, c->dW, c->ld, c->N, pc);
@@ -561,14 +560,14 @@ void solve_alpha_from_z(gpe_ctx* c)
     hipStream_t s = c->stream;
     PhaseScope ps(c, GPE_PH_SOLVE, (double)c->N * c->N * c->P);
     const int64_t nblk = (c->N + NB - 1) / NB;
-    const bool flow = c->flow_solve && nblk <= 256; // every workgroup of the data-flow sweep must be resident
+    const bool flow = c->flow_solve && nblk <= shell::LL_MAX_BLOCKS; // every workgroup of the data-flow sweep must be resident
     for (int p0 = 0; p0 < c->P; p0 += GPE_MAX_P) {
         int pc = std::min(GPE_MAX_P, c->P - p0);
         if (flow) { // reads z straight from the appended rows, leaves the log-likelihood partial sums
-            if (!(c->P == 1 && bwd_chain_sweep(c, s, c->dA + c->N, c->ld, c->dAl, c->al_prefilled ? 1 : 0, c->dOm, c->hScal + 8)))
+            if (!(c->P == 1 && bwd_chain_sweep(c, s, c->dA + c->N, c->ld, c->dAl, c->al_prefilled ? 1 : 0, c->dOm, c->shell.ll_partials())))
                 launch_trsv_bwd_flow(s, c->dA, c->ld, c->N, c->dXinv, c->dA + c->N + p0, c->ld, 1, c->dAl + (int64_t)p0 * c->ld,
                                      c->ld, pc, c->dInfo + 1, c->al_prefilled ? 1 : 0, c->dOm + (int64_t)p0 * c->ld, c->ld,
-                                     c->hScal + 8, p0 > 0 ? 1 : 0);
+                                     c->shell.ll_partials(), p0 > 0 ? 1 : 0);
         }
         else {
             launch_rows_to_cols(s, c->dA + c->N + p0, c->ld, c->N, pc, c->dY, c->ld);
@@ -583,7 +582,7 @@ void enqueue_loglik_terms(gpe_ctx* c)
 {
     PhaseScope ps(c, GPE_PH_LOGLIK, 0.0);
     // flow path: gp.hpp:274-277 from the sweep's per-block partials, which it wrote straight into the pinned
-    // host buffer (hScal + 8); they are added on the host in block order.  Nothing to enqueue.
+    // host buffer (shell.ll_partials()); they are added on the host in block order.  Nothing to enqueue.
     if (c->ll_partials == 0) {
         launch_loglik_terms(c->stream, c->dA, c->ld, c->N, c->dOm, c->dAl, c->ld, c->P, c->dScal);
         hipMemcpyAsync(c->hScal, c->dScal, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -750,8 +749,8 @@ static void sum_ll_partials(gpe_ctx* c)
     if (c->ll_partials > 0) {
         long double sl = 0.0L, sa = 0.0L;
         for (int j = 0; j < c->ll_partials; ++j) {
-            sl += c->hScal[8 + j];
-            sa += c->hScal[8 + c->ll_partials + j];
+            sl += c->shell.ll_partials()[j];
+            sa += c->shell.ll_partials()[c->ll_partials + j];
         }
         c->hScal[0] = (double)sl;
         c->hScal[1] = (double)sa;

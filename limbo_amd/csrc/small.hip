@@ -484,6 +484,7 @@ __global__ __launch_bounds__(SM_T) void k_small_alpha(SmallAlphaArgs g)
 // ---------------------------------------------------------------------------------------------------------------------
 // ---- host side ------------------------------------------------------------------------------------------------------
 int small_max_n() { return SM_NBLK * NB; }
+static_assert(SM_NBLK * NB == shell::SMALL_MAX_N, "the pinned staging region is sized for this order (shell_layout.h)");
 
 void launch_small_add(hipStream_t s, const SmallAddArgs& g, int P, const KParams& kp, const LamParams& lp, const double* x)
 {

@@ -16,6 +16,10 @@ drops or hands on a device buffer (lifecycle_steps); it prints the sha256 of eve
 
 The cases of QUERY_CASES and SPARSE_CASES are about the host side of the query family (limbo_amd/csrc/query.hpp and the calls
 built on its chunk helpers): one line per call with its launches and the sha256 of every array it returned.
+
+The case `shell` is about the handle's shell (limbo_amd/csrc/shell_layout.h: the streams, the device block and the pinned block
+that a destroyed handle leaves to the next one): three handles in a row in one process, each taking the shell of the one before,
+through every region of the two blocks (run_shell_case); one line per call, as the query cases.
 """
 import argparse
 import hashlib
@@ -74,7 +78,8 @@ SPARSE_CASES = {
     "s300": (1300, 300, 130, {}, "the transposed layout: both panel solves of the prediction"),
     "s300c": (1300, 300, 130, {"GPE_SPARSE_CHUNK": "512", "GPE_QUERY_T": "0"}, "... three chunks; transposed whatever GPE_QUERY_T says"),
 }
-ALL_CASES = {**CASES, **QUERY_CASES, **SPARSE_CASES}
+SHELL_CASES = {"shell": ({}, "three handles on one pooled shell: stepped panels with head copy, one-launch panels, the small path")}
+ALL_CASES = {**CASES, **QUERY_CASES, **SPARSE_CASES, **SHELL_CASES}
 D = 4
 NOISE = 0.01
 CHILD_TIMEOUT_S = 180
@@ -252,6 +257,52 @@ def run_sparse_case(np, _capi, name):
         h.close()
 
 
+def run_shell_case(np, _capi, name):
+    """The switches of the panel code are read by gpe_create: set between the creates, they differ from handle to handle."""
+    lib = _capi.load_engine()
+    theta = 0.1 * np.arange(D + 1) - 0.2
+    panel_switches = ("GPE_TAIL_MAX", "GPE_PANEL256", "GPE_PANEL_HANDOVER")
+
+    def call(label, fn, names):
+        res, launches = traced(lib, fn)
+        report(np, name, label, launches, dict(zip(names, res)))
+
+    def evaluate(h):
+        assert h.compute() == 0 and h.flow_retries() == 0 and h.handover_reruns() == 0
+        return np.tril(h.get_L()), h.get_alpha(), np.float64(h.log_lik())
+
+    def panels(tag, env, evaluations):
+        for k in panel_switches:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        h = _capi.Handle(lib, 0)
+        h.set_data(*problem(np, 520, 1, 5000))
+        h.set_kernel(_capi.KERNEL_SE_ARD, theta, NOISE)
+        for i in range(evaluations):
+            call(f"{tag}.compute{i}", lambda: evaluate(h), ("L", "alpha", "log_lik"))
+        h.close()
+
+    # 1. step-by-step panels without the hand-over: the head tiles of both halves are written and copied into the factor
+    panels("stepped", {"GPE_TAIL_MAX": "0", "GPE_PANEL256": "0", "GPE_PANEL_HANDOVER": "0"}, 2)
+    # 2. the pooled shell under the one-launch panels: both polled buffers, the flag tile of a block that has been used
+    panels("panel256", {"GPE_TAIL_MAX": "0"}, 3)
+    # 3. ... and under the small path, P = 2: from an empty model to n = 4, new observations, one point, five points
+    del os.environ["GPE_TAIL_MAX"]
+    X, Y = problem(np, 4, 2, 5001)
+    Xq = np.random.default_rng(5002).uniform(-2.0, 2.0, (5, D))
+    h = _capi.Handle(lib, 0)
+    h.set_kernel(_capi.KERNEL_SE_ARD, theta, NOISE)
+    for n in range(4):
+        call(f"small.add_sample{n}", lambda: (h.add_sample(X[n], Y[: n + 1]), h.get_alpha(), np.float64(h.log_lik())), ("status", "alpha", "log_lik"))
+    call("small.update_alpha", lambda: (h.update_alpha(0.5 - Y), h.get_alpha(), np.float64(h.log_lik())), ("status", "alpha", "log_lik"))
+    call("small.query1", lambda: h.query_batch(Xq[:1]), ("kta", "var"))
+    call("small.query5", lambda: h.query_batch(Xq), ("kta", "var"))
+    # three add_samples, update_alpha and the two queries took the one-launch path: 6 (hashed below, in words on stderr)
+    print(f"shell: {h.small_calls()} calls served by the small path", file=sys.stderr)
+    report(np, name, "small.calls", [], {"small_calls": np.int64(h.small_calls())})
+    h.close()
+
+
 def run_case(name, root):
     sys.path.insert(0, str(root))
     import numpy as np
@@ -265,6 +316,8 @@ def run_case(name, root):
         return run_query_case(np, _capi, name)
     if name in SPARSE_CASES:
         return run_sparse_case(np, _capi, name)
+    if name in SHELL_CASES:
+        return run_shell_case(np, _capi, name)
     N, P, _, _ = CASES[name]
     lib = _capi.load_engine()
     hs = []
