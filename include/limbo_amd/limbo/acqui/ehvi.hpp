@@ -1,0 +1,264 @@
+// limbo/acqui/ehvi.hpp — the exact expected hypervolume improvement of two objectives (include/gpe_ehvi.h,
+// model::GP::expected_hypervolume_improvement).
+// The reference's counterpart is experimental (src/limbo/experimental/acqui/ehvi.hpp over src/ehvi's ehvi2d): two objectives only,
+// an O(n^2) walk over grid cells, and model.sigma(v) — a variance with the noise added — handed to the slot of a standard
+// deviation (ehvi.hpp:76).  Here the value is the O(n) strip sum of positive terms, s is sqrt(variance), and the variance is the
+// latent function's unless the caller asks for the observation's.  Both objectives are maximised, as everywhere in limbo.
+#ifndef LIMBO_AMD_ACQUI_EHVI_HPP
+#define LIMBO_AMD_ACQUI_EHVI_HPP
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <stdexcept>
+#include <type_traits>
+#include <vector>
+
+#include <Eigen/Core>
+
+#include <limbo/acqui/afun_gradient.hpp>
+#include <limbo/model/gp/ehvi.hpp>
+#include <limbo/opt/optimizer.hpp>
+
+#include "../../../gpe_ehvi.h"
+
+namespace limbo_amd {
+    /// The front of `points` (two objectives each) above ref, prepared for the calls below: dominated points, duplicates and points
+    /// not above ref dropped, ascending in the first objective; row-major n x 2.  (gpe_ehvi2_front: host only.)
+    inline std::vector<double> pareto_front2(const std::vector<Eigen::VectorXd>& points, const Eigen::VectorXd& ref)
+    {
+        std::vector<double> F(2 * points.size()), out(2 * points.size() + 2);
+        for (size_t i = 0; i < points.size(); ++i) {
+            F[2 * i] = points[i](0);
+            F[2 * i + 1] = points[i](1);
+        }
+        const double r[2] = {ref(0), ref(1)};
+        int64_t k = 0;
+        if (gpe_ehvi2_front(F.data(), (int64_t)points.size(), r, out.data(), &k) != GPE_OK)
+            throw std::invalid_argument("limbo_amd: pareto_front2(): a NaN among the points, or a reference point that is not finite");
+        out.resize((size_t)(2 * k));
+        return out;
+    }
+    /// the area a prepared front dominates above ref
+    inline double hypervolume2(const std::vector<double>& front, const Eigen::VectorXd& ref)
+    {
+        double hv = 0.0, left = ref(0);
+        for (size_t i = 0; i + 1 < front.size(); i += 2) {
+            hv += (front[i] - left) * (front[i + 1] - ref(1));
+            left = front[i];
+        }
+        return hv;
+    }
+
+    /// ehvi[m] of every candidate under outputs (out1, out2) of ONE model with >= 2 outputs, which share sigma.  observation: the
+    /// kernel's noise is in the variance (default: the latent function).
+    template <typename Params, typename Model>
+    std::vector<double> ehvi2_batch(const Model& model, const std::vector<Eigen::VectorXd>& candidates, const std::vector<double>& front,
+        const Eigen::VectorXd& ref, int out1 = 0, int out2 = 1, bool observation = false)
+    {
+        std::vector<double> ehvi;
+        const double r[2] = {ref(0), ref(1)};
+        model.expected_hypervolume_improvement(candidates, front, r, out1, out2, observation, ehvi);
+        return ehvi;
+    }
+
+    namespace ehvi_detail {
+        // afun(mu) and sigma of every point under one single-objective model: one query_batch
+        template <typename Model, typename AggregatorFunction>
+        void beliefs(const Model& model, const std::vector<Eigen::VectorXd>& pts, const AggregatorFunction& afun, bool observation,
+            std::vector<double>& mu, std::vector<double>& sd)
+        {
+            Eigen::MatrixXd m;
+            Eigen::VectorXd s2;
+            model.query_batch(pts, m, s2);
+            const double noise = model.kernel_function().noise();
+            mu.resize(pts.size());
+            sd.resize(pts.size());
+            for (size_t i = 0; i < pts.size(); ++i) {
+                Eigen::VectorXd row(m.cols());
+                for (int p = 0; p < (int)m.cols(); ++p)
+                    row(p) = m(i, p);
+                mu[i] = afun(row);
+                sd[i] = std::sqrt(observation ? s2(i) : std::max(s2(i) - noise, 0.0));
+            }
+        }
+        // the strip sums of computed beliefs: on the device through whichever model holds an engine, else on the host
+        template <typename Model>
+        void values(const Model& model1, const Model& model2, const std::vector<double>& front, const double* ref, const std::vector<double>& mu1,
+            const std::vector<double>& s1, const std::vector<double>& mu2, const std::vector<double>& s2, std::vector<double>& ehvi,
+            std::vector<double>* partials)
+        {
+            const int64_t M = mu1.size(), n = (int64_t)front.size() / 2;
+            if (front.size() % 2 != 0 || n > GPE_EHVI_MAX_FRONT
+                || gpe_ehvi2_values(nullptr, front.data(), n, ref, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr) != GPE_OK)
+                throw std::invalid_argument("limbo_amd: ehvi2: the front is not prepared (include/gpe_ehvi.h; limbo_amd::pareto_front2 makes one)");
+            if (M == 0) {
+                ehvi.clear();
+                if (partials)
+                    partials->clear();
+                return;
+            }
+            if (model1.has_engine())
+                model1.ehvi2_values(front, ref, mu1, s1, mu2, s2, ehvi, partials);
+            else if (model2.has_engine())
+                model2.ehvi2_values(front, ref, mu1, s1, mu2, s2, ehvi, partials);
+            else {
+                ehvi.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign((size_t)(4 * M), 0.0);
+                ehvi_host::strip_sums(front.data(), n, ref, mu1.data(), s1.data(), mu2.data(), s2.data(), M, ehvi.data(),
+                    partials ? partials->data() : nullptr);
+            }
+        }
+    } // namespace ehvi_detail
+
+    /// ehvi[m] under TWO single-objective models (the reference's Ehvi(models, pop, ref)): objective k is afun(mu) of model k with
+    /// that model's own sigma.  One query_batch each, then the strip sums.
+    template <typename Params, typename Model, typename AggregatorFunction = FirstElem>
+    std::vector<double> ehvi2_batch(const Model& model1, const Model& model2, const std::vector<Eigen::VectorXd>& candidates,
+        const std::vector<double>& front, const Eigen::VectorXd& ref, const AggregatorFunction& afun = AggregatorFunction(), bool observation = false)
+    {
+        std::vector<double> mu1, s1, mu2, s2, ehvi;
+        const double r[2] = {ref(0), ref(1)};
+        if (!candidates.empty()) {
+            ehvi_detail::beliefs(model1, candidates, afun, observation, mu1, s1);
+            ehvi_detail::beliefs(model2, candidates, afun, observation, mu2, s2);
+        }
+        ehvi_detail::values(model1, model2, front, r, mu1, s1, mu2, s2, ehvi, nullptr);
+        return ehvi;
+    }
+
+    /// the index of the largest value (the lowest one on exact ties), -1 without candidates
+    inline int64_t ehvi2_best(const std::vector<double>& ehvi)
+    {
+        int64_t best = -1;
+        for (size_t m = 0; m < ehvi.size(); ++m)
+            if (best < 0 || ehvi[m] > ehvi[(size_t)best])
+                best = (int64_t)m;
+        return best;
+    }
+    template <typename Params, typename Model>
+    int64_t ehvi2_best(const Model& model, const std::vector<Eigen::VectorXd>& candidates, const std::vector<double>& front,
+        const Eigen::VectorXd& ref, int out1 = 0, int out2 = 1, bool observation = false)
+    {
+        return ehvi2_best(ehvi2_batch<Params>(model, candidates, front, ref, out1, out2, observation));
+    }
+    template <typename Params, typename Model, typename AggregatorFunction = FirstElem>
+    int64_t ehvi2_best(const Model& model1, const Model& model2, const std::vector<Eigen::VectorXd>& candidates, const std::vector<double>& front,
+        const Eigen::VectorXd& ref, const AggregatorFunction& afun = AggregatorFunction(), bool observation = false)
+    {
+        return ehvi2_best(ehvi2_batch<Params>(model1, model2, candidates, front, ref, afun, observation));
+    }
+} // namespace limbo_amd
+
+namespace limbo {
+    namespace acqui {
+        /// The acquisition object over two single-objective models, a prepared front and a reference point.  The aggregator is
+        /// applied to each model's mean.  observation (constructor flag): the kernel's noise is in the variance; default: the
+        /// latent function.  opt::make_batch_objective takes it as any other acquisition object.
+        template <typename Params, typename Model>
+        class Ehvi2 {
+        public:
+            Ehvi2(const Model& model1, const Model& model2, const std::vector<double>& front, const Eigen::VectorXd& ref, bool observation = false)
+                : _m1(model1), _m2(model2), _front(front), _observation(observation)
+            {
+                _ref[0] = ref(0);
+                _ref[1] = ref(1);
+            }
+            size_t dim_in() const { return _m1.dim_in(); }
+            size_t dim_out() const { return 2; }
+
+            template <typename AggregatorFunction>
+            std::vector<double> batch(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun) const
+            {
+                std::vector<double> mu1, s1, mu2, s2, ehvi;
+                if (!points.empty()) {
+                    limbo_amd::ehvi_detail::beliefs(_m1, points, afun, _observation, mu1, s1);
+                    limbo_amd::ehvi_detail::beliefs(_m2, points, afun, _observation, mu2, s2);
+                }
+                limbo_amd::ehvi_detail::values(_m1, _m2, _front, _ref, mu1, s1, mu2, s2, ehvi, nullptr);
+                return ehvi;
+            }
+
+            /// values[m] as batch(); grads[m] = sum over the two objectives k of (d/d mu_k) grad mu_k + (d/d s_k) grad sigma_k^2 /
+            /// (2 s_k), mu_k = afun(mu of model k), its derivative through limbo_amd::afun_gradient; the term in s_k is zero where
+            /// s_k is (the clamp).  One query_grad_batch per model, then the strip sums with their four partials.  The mean
+            /// functor's own derivative is not included (GP::query_grad_batch).
+            template <typename AggregatorFunction>
+            void batch_grad(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun, std::vector<double>& values,
+                std::vector<Eigen::VectorXd>& grads) const
+            {
+                const size_t M = points.size();
+                const int D = (int)_m1.dim_in();
+                std::vector<double> mu[2], sd[2], part;
+                std::vector<Eigen::VectorXd> gmu[2]; // d afun(mu) / d v
+                Eigen::MatrixXd ds2[2];
+                const Model* md[2] = {&_m1, &_m2};
+                for (int k = 0; k < 2 && M > 0; ++k) {
+                    Eigen::MatrixXd m;
+                    Eigen::VectorXd s2;
+                    std::vector<Eigen::MatrixXd> dmu;
+                    md[k]->query_grad_batch(points, m, s2, dmu, ds2[k]);
+                    const double noise = md[k]->kernel_function().noise();
+                    mu[k].resize(M);
+                    sd[k].resize(M);
+                    gmu[k].resize(M);
+                    for (size_t i = 0; i < M; ++i) {
+                        Eigen::VectorXd row(m.cols());
+                        for (int p = 0; p < (int)m.cols(); ++p)
+                            row(p) = m(i, p);
+                        mu[k][i] = afun(row);
+                        sd[k][i] = std::sqrt(_observation ? s2(i) : std::max(s2(i) - noise, 0.0));
+                        const Eigen::VectorXd da = limbo_amd::afun_gradient(afun, row);
+                        Eigen::VectorXd g = Eigen::VectorXd::Zero(D);
+                        for (int d = 0; d < D; ++d)
+                            for (int p = 0; p < (int)m.cols(); ++p)
+                                g(d) += da(p) * dmu[i](p, d);
+                        gmu[k][i] = g;
+                    }
+                }
+                limbo_amd::ehvi_detail::values(_m1, _m2, _front, _ref, mu[0], sd[0], mu[1], sd[1], values, &part);
+                grads.resize(M);
+                for (size_t i = 0; i < M; ++i) {
+                    Eigen::VectorXd g = Eigen::VectorXd::Zero(D);
+                    for (int k = 0; k < 2; ++k)
+                        for (int d = 0; d < D; ++d) {
+                            g(d) += part[i + M * (size_t)(2 * k)] * gmu[k][i](d);
+                            if (sd[k][i] > 0.0)
+                                g(d) += part[i + M * (size_t)(2 * k + 1)] * ds2[k](i, d) / (2.0 * sd[k][i]);
+                        }
+                    grads[i] = g;
+                }
+            }
+
+            template <typename AggregatorFunction>
+            opt::eval_t operator()(const Eigen::VectorXd& v, const AggregatorFunction& afun, bool gradient) const
+            {
+                if (gradient)
+                    return _one_with_gradient(v, afun, limbo_amd::afun_differentiable<AggregatorFunction>());
+                return opt::no_grad(batch(std::vector<Eigen::VectorXd>(1, v), afun)[0]);
+            }
+
+        protected:
+            const Model& _m1;
+            const Model& _m2;
+            std::vector<double> _front;
+            double _ref[2];
+            bool _observation;
+
+            template <typename AggregatorFunction>
+            opt::eval_t _one_with_gradient(const Eigen::VectorXd& v, const AggregatorFunction& afun, std::true_type) const
+            {
+                std::vector<double> val;
+                std::vector<Eigen::VectorXd> gr;
+                batch_grad(std::vector<Eigen::VectorXd>(1, v), afun, val, gr);
+                return opt::eval_t{val[0], opt::eval_t::second_type(gr[0])};
+            }
+            template <typename AggregatorFunction>
+            opt::eval_t _one_with_gradient(const Eigen::VectorXd&, const AggregatorFunction&, std::false_type) const
+            {
+                throw std::logic_error("limbo_amd: acqui::Ehvi2 with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
+            }
+        };
+    } // namespace acqui
+} // namespace limbo
+#endif

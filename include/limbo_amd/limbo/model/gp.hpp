@@ -57,6 +57,7 @@
 #include <limbo/model/gp/query_grad.hpp>
 #include <limbo/model/gp/pathwise.hpp>
 #include <limbo/model/gp/kg.hpp>
+#include <limbo/model/gp/ehvi.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -69,6 +70,7 @@
 #include "../../../gpe_query_grad.h"
 #include "../../../gpe_batch_select.h"
 #include "../../../gpe_kg.h"
+#include "../../../gpe_ehvi.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -588,6 +590,71 @@ namespace limbo {
                 std::vector<double>& kg) const
             {
                 knowledge_gradient(alternatives, candidates, {}, {}, _kernel_function.noise(), with_self, kg);
+            }
+
+            /// Addition (include/gpe_ehvi.h, model/gp/ehvi.hpp): the exact expected hypervolume improvement of every candidate
+            /// under TWO outputs of this model (out1 != out2, both maximised; they share sigma: limbo's GP with dim_out = 2) over
+            /// a prepared front (row-major n x 2: ascending in output out1, descending in out2, all above ref; limbo_amd::
+            /// pareto_front2 makes one).  The means are k^T alpha plus the mean functor; sigma^2 is the clamped variance of the
+            /// LATENT function, or, observation == true, with the kernel's noise added (what query() reports).  Unlike the
+            /// reference's experimental/acqui/ehvi.hpp:76 the strip sum is given a standard deviation, not sigma(v).  partials
+            /// (may be null): M x 4 column-major, d/d mu1, d/d s1, d/d mu2, d/d s2.  The model is not changed.  On the model's
+            /// home device; no samples (the prior), a host-resident model below the batch crossover and kernels without device
+            /// code: query_batch() and the host strip sum of the same definition.
+            void expected_hypervolume_improvement(const std::vector<Eigen::VectorXd>& candidates, const std::vector<double>& front,
+                const double* ref, int out1, int out2, bool observation, std::vector<double>& ehvi, std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = candidates.size(), n = (int64_t)front.size() / 2;
+                if (front.size() % 2 != 0 || out1 == out2 || out1 < 0 || out2 < 0 || out1 >= _dim_out || out2 >= _dim_out || !ref
+                    || n > GPE_EHVI_MAX_FRONT || gpe_ehvi2_values(nullptr, front.data(), n, ref, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr) != GPE_OK)
+                    throw std::invalid_argument("limbo_amd: expected_hypervolume_improvement(): bad argument (include/gpe_ehvi.h)");
+                ehvi.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign((size_t)(4 * M), 0.0);
+                if (M == 0)
+                    return;
+                const double noise = _kernel_function.noise();
+                if (_joint_on_host(M)) {
+                    Eigen::MatrixXd mu;
+                    Eigen::VectorXd s2;
+                    query_batch(candidates, mu, s2);
+                    std::vector<double> m1((size_t)M), m2((size_t)M), sd((size_t)M);
+                    for (int64_t m = 0; m < M; ++m) {
+                        m1[(size_t)m] = mu(m, out1);
+                        m2[(size_t)m] = mu(m, out2);
+                        sd[(size_t)m] = std::sqrt(observation ? s2(m) : std::max(s2(m) - noise, 0.0));
+                    }
+                    limbo_amd::ehvi_host::strip_sums(front.data(), n, ref, m1.data(), sd.data(), m2.data(), sd.data(), M, ehvi.data(),
+                        partials ? partials->data() : nullptr);
+                    return;
+                }
+                const std::vector<double> Xc = _joint_points(candidates);
+                std::vector<double> add((size_t)(2 * M));
+                for (int64_t m = 0; m < M; ++m) {
+                    const Eigen::VectorXd mv = _mean_function(candidates[(size_t)m], *this);
+                    add[(size_t)m] = mv(out1);
+                    add[(size_t)(M + m)] = mv(out2);
+                }
+                _eng.check(gpe_ehvi2_batch(_eng.get(), out1, out2, Xc.data(), M, add.data(), observation ? noise : 0.0, front.data(), n, ref,
+                               ehvi.data(), partials ? partials->data() : nullptr, nullptr, nullptr),
+                    "gpe_ehvi2_batch");
+            }
+            /// Does this model hold an engine handle a caller's own beliefs can be scored through (ehvi2_values)?
+            bool has_engine() const
+            {
+                return !_host_mode && _eng.peek() != nullptr && limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K;
+            }
+            /// gpe_ehvi2_values through this model's engine handle (has_engine()): the strip sums of beliefs the caller computed
+            void ehvi2_values(const std::vector<double>& front, const double* ref, const std::vector<double>& mu1, const std::vector<double>& s1,
+                const std::vector<double>& mu2, const std::vector<double>& s2, std::vector<double>& ehvi, std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = mu1.size();
+                ehvi.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign((size_t)(4 * M), 0.0);
+                _eng.check(gpe_ehvi2_values(_eng.get(), front.data(), (int64_t)front.size() / 2, ref, mu1.data(), s1.data(), mu2.data(), s2.data(), M,
+                               ehvi.data(), partials ? partials->data() : nullptr),
+                    "gpe_ehvi2_values");
             }
 
             /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise

@@ -24,6 +24,7 @@ SELECT_UCB, SELECT_EI, SELECT_VAR = range(3)  # include/gpe_batch_select.h: the 
 REMOVE_AUTO, REMOVE_UPDATE, REMOVE_RECOMPUTE = range(3)  # include/gpe_remove.h: the `how` of remove_samples
 REMOVE_HOW = {"auto": 0, "update": 1, "recompute": 2}
 KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
+EHVI_MAX_FRONT = 2048  # include/gpe_ehvi.h: GPE_EHVI_MAX_FRONT
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -159,6 +160,11 @@ def _sig(lib, prefix):
             "kg_batch": [_vp, _dp, _i64, _dp, _dp, _i64, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _i64],
             "kg_envelope": [_vp, _dp, _i64, _dp, _i64, _i64, _dp, C.POINTER(C.c_int32)],
             "kg_phase_ms": [_vp, _dp],
+            # include/gpe_ehvi.h: the two-objective expected hypervolume improvement over a Pareto front
+            "ehvi2_front": [_dp, _i64, _dp, _dp, C.POINTER(_i64)],
+            "ehvi2_values": [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _i64, _dp, _dp],
+            "ehvi2_batch": [_vp, C.c_int, C.c_int, _dp, _i64, _dp, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp],
+            "ehvi_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -200,6 +206,24 @@ def _d(a):
 
 def _c(a, order="C"):
     return np.require(np.asarray(a, dtype=np.float64), requirements=["C" if order == "C" else "F", "A"])
+
+
+def _front_args(front, ref):
+    F = _c(np.asarray(front, dtype=np.float64).reshape(-1, 2))
+    r = _c(np.asarray(ref, dtype=np.float64).reshape(2))
+    return F, r
+
+
+def ehvi2_front(points, ref, check=True):
+    """gpe_ehvi2_front (include/gpe_ehvi.h; host only, no handle): the Pareto front of `points` (n x 2, both objectives maximised)
+    above ref — dominated points, duplicates and points not above ref dropped, ascending in f1.  Returns (status, front (k, 2))."""
+    F, r = _front_args(points, ref)
+    out = np.zeros((max(F.shape[0], 1), 2))
+    k = _i64(0)
+    rc = load_engine().fn("ehvi2_front")(_d(F), F.shape[0], _d(r), _d(out), C.byref(k))
+    if check and rc < 0:
+        raise EngineError(f"gpe_ehvi2_front failed: status {rc}")
+    return rc, out[: k.value].copy()
 
 
 class Handle:
@@ -533,6 +557,45 @@ class Handle:
         ms = np.zeros(4)
         self._chk(self.lib.fn("kg_phase_ms")(self._h, _d(ms)), "kg_phase_ms")
         return dict(zip(("alternatives", "candidates", "envelope", "readback"), ms.tolist()))
+
+    # -- the two-objective expected hypervolume improvement (include/gpe_ehvi.h; HIP library only)
+    def ehvi2_values(self, front, ref, mu1, s1, mu2, s2, want_partials=True, check=True):
+        """The strip sums alone on host-supplied beliefs (s: standard deviations) over a prepared front (n x 2; ehvi2_front makes
+        one); any handle serves.  Returns (status, ehvi (M), partials (M, 4: d/d mu1, s1, mu2, s2) or None).  check=False hands a
+        negative GPE_ERR_* back instead of raising."""
+        F, r = _front_args(front, ref)
+        b = [_c(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (mu1, s1, mu2, s2)]
+        M = b[0].shape[0]
+        assert all(v.shape[0] == M for v in b)
+        ehvi = np.zeros(M)
+        part = np.zeros((M, 4), order="F") if want_partials else None
+        rc = self.lib.fn("ehvi2_values")(self._h, _d(F), F.shape[0], _d(r), _d(b[0]), _d(b[1]), _d(b[2]), _d(b[3]), M, _d(ehvi),
+                                         _d(part) if want_partials else None)
+        if check:
+            self._chk(rc, "ehvi2_values")
+        return rc, ehvi, part
+
+    def ehvi2_batch(self, Xc, front, ref, out1=0, out2=1, mean_add=None, var_add=0.0, want=("ehvi", "partials", "mu", "var"), check=True):
+        """The expected hypervolume improvement of every row of Xc under the handle's outputs (out1, out2), which share sigma.
+        mean_add: (M, 2) added to k^T alpha, or None; var_add: added to the clamped variance (0: the latent function).  Returns
+        (status, ehvi (M), partials (M, 4), mu (M, 2), var (M)), None for what `want` leaves out."""
+        Xc = _c(Xc).reshape(-1, self.D)
+        M = Xc.shape[0]
+        F, r = _front_args(front, ref)
+        ma = _c(np.asarray(mean_add, dtype=np.float64).reshape(M, 2), "F") if mean_add is not None else None
+        out = {"ehvi": np.zeros(M), "partials": np.zeros((M, 4), order="F"), "mu": np.zeros((M, 2), order="F"), "var": np.zeros(M)}
+        ptr = [_d(out[k]) if k in want else None for k in ("ehvi", "partials", "mu", "var")]
+        rc = self.lib.fn("ehvi2_batch")(self._h, int(out1), int(out2), _d(Xc), M, _d(ma) if ma is not None else None, float(var_add), _d(F),
+                                        F.shape[0], _d(r), *ptr)
+        if check:
+            self._chk(rc, "ehvi2_batch")
+        return (rc,) + tuple(out[k] if k in want else None for k in ("ehvi", "partials", "mu", "var"))
+
+    def ehvi_phase_ms(self):
+        """{solves, kernel, readback} of the last ehvi2_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("ehvi_phase_ms")(self._h, _d(ms)), "ehvi_phase_ms")
+        return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
 
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)
     def query_batch_grad(self, Xq, want=("kta", "var", "dkta", "dvar")):

@@ -544,6 +544,24 @@ void launch_sel_round(hipStream_t s, const SelRound& g, int t); // round t: gath
 void launch_kg_envelope(hipStream_t s, const double* a, int A, const double* B, int64_t ldb, int64_t M, const double* var, double obs_noise,
                         int with_self, const double* mu_c, double* kg, int* nseg);
 
+// ---- the two-objective expected hypervolume improvement (ehvi.hip; include/gpe_ehvi.h) ----------------------------------
+// ehvi[m] and, partials != null, the four partials (column c at partials + c ldp) of candidate m < M over the prepared front
+// (device, row-major n x 2, n <= GPE_EHVI_MAX_FRONT: it sits in LDS) and (r1, r2); one wave each.  The belief of candidate m:
+// means mu1[m] (+ add1[m]) and mu2[m] (+ add2[m]; add1 == null: nothing is added); var == null: the standard deviations s1[m], s2[m];
+// otherwise both are sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  mu_out (may be null): the two means as used, column k at
+// mu_out + k ldm.
+struct EhviArgs {
+    const double* front;
+    int n;
+    double r1, r2;
+    const double *mu1, *mu2, *add1, *add2, *s1, *s2, *var;
+    double var_add;
+    int64_t M;
+    double *ehvi, *partials, *mu_out;
+    int64_t ldp, ldm;
+};
+void launch_ehvi2(hipStream_t s, const EhviArgs& q);
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);

@@ -1,0 +1,182 @@
+// ehvi.hip — the exact two-objective expected hypervolume improvement (include/gpe_ehvi.h): the strip kernel.
+//
+//   ehvi[m] = sum_{i = 0 .. n} (psi_1(l_i) - psi_1(l_{i+1})) psi_2(h_i),   psi_k(t) = s_k f((mu_k - t) / s_k),  f(z) = phi(z) + z Phi(z)
+//
+// l_0 = r1, l_i = y1(i), l_{n+1} = +inf (psi_1 = 0); h_i = y2(i+1), h_n = r2: strip i is the band l_i <= f1 < l_{i+1} above which
+// the front reaches h_i.  psi falls with t, l rises, h falls: every term is positive (the reference's cell walk subtracts two
+// products per cell and returns 0 where the value is 1e-60).  The partials in (mu2, s2) put Phi_2 / phi_2 in psi_2's place; those in
+// (mu1, s1) are the same sum by parts, sum_i {Phi_1, phi_1}(l_i) (psi_2(h_i) - psi_2(h_{i-1})), psi_2(h_{-1}) = 0 — positive terms
+// again, where the term-by-term derivative phi_1(l_i) - phi_1(l_{i+1}) changes sign.
+//
+// One wave per candidate, EHVI_W candidates per workgroup; the front sits in LDS as (y1, y2) pairs, shared by the waves.  Index
+// i = 0 .. n + 1 goes to lane i mod 64 in rounds; the lane evaluates (psi, Phi, phi) of objective 1 at l_i and of objective 2 at
+// h_i — two exp + erfc pairs — and takes index i - 1's values from the lane below (lane 0: from lane 63 of the round before).  With
+// them it adds strip i - 1's term to the sums in (value, mu2, s2) and index i's to those in (mu1, s1).  Five accumulators per lane,
+// ascending i; then one fixed xor tree over the 64 lanes and lane 0 stores.  The rounds are (n + 2 + 63) / 64 whatever the inputs;
+// no workgroup waits for another; no atomics.  Nothing here is chosen from M.
+#include <cfloat>
+
+#include "dev.h"
+
+namespace {
+constexpr int EHVI_W = 4;            // waves = candidates per workgroup
+constexpr int EHVI_T = 64 * EHVI_W;  // threads per workgroup
+
+struct Ev {
+    double psi, Phi, phi;
+};
+} // namespace
+
+// (psi, Phi, phi) of the belief (mu, s) at the finite threshold t.  z < 0: f = phi + z Phi(z), which loses about z^2 ulps to
+// cancellation at large |z| (kg.hip: kg_f); z >= 0: f = z + f(-z).  s = 0: the limit.  A NaN anywhere: NaN.
+static __device__ __forceinline__ Ev ehvi_ev(double mu, double s, double t)
+{
+    Ev e;
+    const double d = mu - t;
+    if (!(s > 0.0)) {
+        if (s != s || d != d || s < 0.0)
+            e.psi = e.Phi = e.phi = __longlong_as_double(0x7ff8000000000000LL);
+        else {
+            e.psi = d > 0.0 ? d : 0.0;
+            e.Phi = d > 0.0 ? 1.0 : 0.0;
+            e.phi = 0.0;
+        }
+        return e;
+    }
+    const double z = d / s;
+    if (z != z) {
+        e.psi = e.Phi = e.phi = z;
+        return e;
+    }
+    const double a = -fabs(z);
+    double fm = 0.0, Q = 0.0, phi = 0.0; // f(-|z|), Phi(-|z|), phi(z); all 0 at |z| = inf
+    if (a >= -DBL_MAX) {
+        phi = exp(-0.5 * a * a) * 0.39894228040143267794; // 1 / sqrt(2 pi)
+        Q = 0.5 * erfc(-a * 0.70710678118654752440);
+        fm = fmax(phi + a * Q, 0.0);
+    }
+    e.phi = phi;
+    e.Phi = z < 0.0 ? Q : 1.0 - Q;
+    e.psi = s * (z < 0.0 ? fm : z + fm);
+    return e;
+}
+// x y, with 0 inf = 0 (a strip of no width under an unbounded height, and the other way round); a NaN factor stays NaN
+static __device__ __forceinline__ double ehvi_mul(double x, double y)
+{
+    const double p = x * y;
+    return (p != p && x == x && y == y) ? 0.0 : p;
+}
+// hi - lo >= 0 of two values of a falling psi; both +inf (mu = +inf): the limit, the width `w` of the interval itself
+static __device__ __forceinline__ double ehvi_drop(double hi, double lo, double w)
+{
+    const double d = hi - lo;
+    if (d != d && hi == hi && lo == lo)
+        return w;
+    return d < 0.0 ? 0.0 : d;
+}
+
+__global__ __launch_bounds__(EHVI_T) void k_ehvi2(EhviArgs q)
+{
+    extern __shared__ double2 ehvi_front[];
+    const int n = q.n;
+    for (int i = threadIdx.x; i < n; i += EHVI_T)
+        ehvi_front[i] = make_double2(q.front[2 * i], q.front[2 * i + 1]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t m = (int64_t)blockIdx.x * EHVI_W + (threadIdx.x >> 6);
+    if (m >= q.M) // (wave-uniform; no barrier follows)
+        return;
+
+    double mu1 = q.mu1[m], mu2 = q.mu2[m], s1, s2;
+    if (q.add1) {
+        mu1 += q.add1[m];
+        mu2 += q.add2[m];
+    }
+    if (q.var) { // one model, two outputs: the shared sigma, clamped as gp.hpp:621-623
+        const double v = q.var[m];
+        s1 = s2 = sqrt((v > DBL_EPSILON ? v : (v != v ? v : 0.0)) + q.var_add);
+    }
+    else {
+        s1 = q.s1[m];
+        s2 = q.s2[m];
+    }
+    const double r1 = q.r1, r2 = q.r2, inf = __longlong_as_double(0x7ff0000000000000LL);
+
+    double av = 0.0, am1 = 0.0, as1 = 0.0, am2 = 0.0, as2 = 0.0;
+    double cA = 0.0, cPsi = 0.0, cPhi = 0.0, cphi = 0.0; // index i - 1 of lane 0: lane 63 of the round before
+    const int rounds = (n + 2 + 63) / 64;
+    for (int r = 0; r < rounds; ++r) {
+        const int i = r * 64 + lane;
+        Ev e1{0.0, 0.0, 0.0}, e2{0.0, 0.0, 0.0};
+        double l = inf, lp = r1, h = r2, hp = r2; // l_i, l_{i-1}, h_i, h_{i-1}
+        if (i <= n) {
+            if (i >= 1) {
+                const double2 p = ehvi_front[i - 1];
+                l = p.x;
+                hp = p.y;
+            }
+            else
+                l = r1;
+            if (i >= 2)
+                lp = ehvi_front[i - 2].x;
+            if (i < n)
+                h = ehvi_front[i].y;
+            e1 = ehvi_ev(mu1, s1, l);
+            e2 = ehvi_ev(mu2, s2, h);
+        }
+        else if (i == n + 1 && n >= 1)
+            lp = ehvi_front[n - 1].x;
+        // index i - 1's values (every lane takes part in the shuffles)
+        double pA = __shfl_up(e1.psi, 1), pPsi = __shfl_up(e2.psi, 1), pPhi = __shfl_up(e2.Phi, 1), pphi = __shfl_up(e2.phi, 1);
+        if (lane == 0) {
+            pA = cA;
+            pPsi = cPsi;
+            pPhi = cPhi;
+            pphi = cphi;
+        }
+        cA = __shfl(e1.psi, 63);
+        cPsi = __shfl(e2.psi, 63);
+        cPhi = __shfl(e2.Phi, 63);
+        cphi = __shfl(e2.phi, 63);
+        if (i >= 1 && i <= n + 1) { // strip i - 1: l_{i-1} <= f1 < l_i at height h_{i-1}
+            const double w = ehvi_drop(pA, e1.psi, l - lp);
+            av += ehvi_mul(w, pPsi);
+            am2 += ehvi_mul(w, pPhi);
+            as2 += ehvi_mul(w, pphi);
+        }
+        if (i <= n) { // by parts: index i
+            const double v = i == 0 ? e2.psi : ehvi_drop(e2.psi, pPsi, hp - h);
+            am1 += ehvi_mul(e1.Phi, v);
+            as1 += ehvi_mul(e1.phi, v);
+        }
+    }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) {
+        av += __shfl_xor(av, w);
+        am1 += __shfl_xor(am1, w);
+        as1 += __shfl_xor(as1, w);
+        am2 += __shfl_xor(am2, w);
+        as2 += __shfl_xor(as2, w);
+    }
+    if (lane != 0)
+        return;
+    q.ehvi[m] = av;
+    if (q.partials) {
+        q.partials[m] = am1;
+        q.partials[m + q.ldp] = as1;
+        q.partials[m + 2 * q.ldp] = am2;
+        q.partials[m + 3 * q.ldp] = as2;
+    }
+    if (q.mu_out) {
+        q.mu_out[m] = mu1;
+        q.mu_out[m + q.ldm] = mu2;
+    }
+}
+
+void launch_ehvi2(hipStream_t s, const EhviArgs& q)
+{
+    if (q.M <= 0 || q.n < 0)
+        return;
+    const size_t lds = sizeof(double2) * (size_t)(q.n > 0 ? q.n : 1);
+    GPE_LAUNCH(k_ehvi2, dim3((unsigned)((q.M + EHVI_W - 1) / EHVI_W)), dim3(EHVI_T), lds, s, q);
+}
