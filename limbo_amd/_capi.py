@@ -25,6 +25,7 @@ REMOVE_AUTO, REMOVE_UPDATE, REMOVE_RECOMPUTE = range(3)  # include/gpe_remove.h:
 REMOVE_HOW = {"auto": 0, "update": 1, "recompute": 2}
 KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 EHVI_MAX_FRONT = 2048  # include/gpe_ehvi.h: GPE_EHVI_MAX_FRONT
+CEI_MAX_CONSTRAINTS = 16  # include/gpe_cei.h: GPE_CEI_MAX_CONSTRAINTS
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -165,6 +166,11 @@ def _sig(lib, prefix):
             "ehvi2_values": [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _i64, _dp, _dp],
             "ehvi2_batch": [_vp, C.c_int, C.c_int, _dp, _i64, _dp, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp],
             "ehvi_phase_ms": [_vp, _dp],
+            # include/gpe_cei.h: constrained expected improvement in the log domain
+            "logcei_values": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _i64, _dp, _dp, _dp],
+            "logcei_batch": [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp, _i64, _dp, C.c_double,
+                             _dp, _dp, _dp, _dp, _dp],
+            "cei_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -595,6 +601,62 @@ class Handle:
         """{solves, kernel, readback} of the last ehvi2_batch call in ms (set_profiling(True) first)."""
         ms = np.zeros(3)
         self._chk(self.lib.fn("ehvi_phase_ms")(self._h, _d(ms)), "ehvi_phase_ms")
+        return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
+
+    # -- constrained expected improvement in the log domain (include/gpe_cei.h; HIP library only)
+    def logcei_values(self, thr, mu_c, s_c, mu0=None, s0=None, f_best=0.0, xi=0.0, with_ei=True, want=("terms", "partials"), check=True):
+        """The kernel alone on host-supplied beliefs (s: standard deviations): constraints k feasible when c_k >= thr[k], beliefs
+        mu_c, s_c (M, C); the objective's belief mu0, s0 (M) against the incumbent f_best (not read when with_ei is false).  Any
+        handle serves.  Returns (status, logcei (M), terms (M, 1 + C) or None, partials (M, 2 + 2 C) or None).  check=False hands a
+        negative GPE_ERR_* back instead of raising."""
+        t = _c(np.asarray(thr, dtype=np.float64).reshape(-1))
+        Cn = t.shape[0]
+        if mu0 is not None:
+            m0, sd0 = (_c(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (mu0, s0))
+            M = m0.shape[0]
+            assert sd0.shape[0] == M
+        else:
+            m0 = sd0 = None
+            M = np.asarray(mu_c).reshape(-1, max(Cn, 1)).shape[0] if Cn else 0
+        mc, sc = (_c(np.asarray(v, dtype=np.float64).reshape(M, Cn), "F") for v in (mu_c, s_c))
+        val = np.zeros(M)
+        terms = np.zeros((M, 1 + Cn), order="F") if "terms" in want else None
+        part = np.zeros((M, 2 + 2 * Cn), order="F") if "partials" in want else None
+        opt = lambda a: _d(a) if a is not None and a.size else None
+        rc = self.lib.fn("logcei_values")(self._h, int(bool(with_ei)), float(f_best), float(xi), Cn, opt(t), opt(m0), opt(sd0), opt(mc), opt(sc),
+                                          M, _d(val), opt(terms), opt(part))
+        if check:
+            self._chk(rc, "logcei_values")
+        return rc, val, terms, part
+
+    def logcei_batch(self, Xc, thr, con_outs, out0=0, f_best=0.0, xi=0.0, with_ei=True, mean_add=None, var_add=0.0,
+                     want=("logcei", "terms", "partials", "mu", "var"), check=True):
+        """The log constrained expected improvement of every row of Xc under the handle's output out0 (the objective) and outputs
+        con_outs (the constraints, thresholds thr), which share sigma.  mean_add: (M, 1 + C) added to k^T alpha, or None; var_add:
+        added to the clamped variance (0: the latent function).  Returns (status, logcei (M), terms (M, 1 + C), partials
+        (M, 2 + 2 C), mu (M, 1 + C), var (M)), None for what `want` leaves out."""
+        Xc = _c(Xc).reshape(-1, self.D)
+        M = Xc.shape[0]
+        t = _c(np.asarray(thr, dtype=np.float64).reshape(-1))
+        Cn = t.shape[0]
+        outs = np.ascontiguousarray(np.asarray(con_outs, dtype=np.int32).reshape(-1))
+        assert outs.shape[0] == Cn
+        ma = _c(np.asarray(mean_add, dtype=np.float64).reshape(M, 1 + Cn), "F") if mean_add is not None else None
+        names = ("logcei", "terms", "partials", "mu", "var")
+        out = {"logcei": np.zeros(M), "terms": np.zeros((M, 1 + Cn), order="F"), "partials": np.zeros((M, 2 + 2 * Cn), order="F"),
+               "mu": np.zeros((M, 1 + Cn), order="F"), "var": np.zeros(M)}
+        ptr = [_d(out[k]) if k in want else None for k in names]
+        rc = self.lib.fn("logcei_batch")(self._h, int(bool(with_ei)), int(out0), float(f_best), float(xi), Cn,
+                                         outs.ctypes.data_as(C.POINTER(C.c_int)) if Cn else None, _d(t) if Cn else None, _d(Xc), M,
+                                         _d(ma) if ma is not None else None, float(var_add), *ptr)
+        if check:
+            self._chk(rc, "logcei_batch")
+        return (rc,) + tuple(out[k] if k in want else None for k in names)
+
+    def cei_phase_ms(self):
+        """{solves, kernel, readback} of the last logcei_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("cei_phase_ms")(self._h, _d(ms)), "cei_phase_ms")
         return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
 
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)

@@ -1,0 +1,183 @@
+// cei.hip — constrained expected improvement in the log domain (include/gpe_cei.h): the kernel.
+//
+//   logcei[m] = [with_ei] (log s0 + log h(z)) + sum_k log Phi(u_k),   h(z) = phi(z) + z Phi(z),  z = (mu0 - f_best - xi) / s0,
+//                                                                     u_k = (mu_k - t_k) / s_k
+//
+// h is the difference of two nearly equal numbers for z < 0 and underflows to 0 below z = -38.6 (acqui::EI, kg.hip's kg_f and
+// ehvi.hip's ehvi_ev form it as written and say so).  Here, for z < -CEI_XC, with x = -z and Mills' ratio R(x) = Phi(-x) / phi(x),
+//   h(z) = Phi(z) T(x),  T(x) = 1 / R(x) - x = 1 / (x + 2 / (x + 3 / (x + ...))),   1 / R(x) = x + T(x)
+// every partial quotient positive, nothing subtracted:
+//   log Phi(-x) = -x^2 / 2 - log sqrt(2 pi) - log(x + T)        lambda(-x) = phi / Phi = x + T
+//   log h(-x)   = log Phi(-x) - log(1 / T)                      Phi / h = 1 / T,  phi / h = (x + T) / T
+// The fraction is evaluated bottom-up from quotient CEI_DEPTH whatever x is: at x = CEI_XC that leaves 2.4e-17 of T, less
+// at every larger x, and at x = 1e100 every step is x + k / x = x.  Above the crossover the direct forms: phi - |z| Q(|z|) cancels
+// at most 1 / (1 - 3 R(3)) = 11.6 times there, and for z >= 0 it is added to z.
+//
+// One thread per candidate, 64 per workgroup (one wave: 16 384 candidates are 256 waves, one per compute unit — the thread's work
+// is a chain of dependent fp64 divisions, so waves spread out finish sooner than waves packed).  The beliefs are column-major: a
+// wave's loads are contiguous.  The loop over the constraints has the wave-uniform bound C; thresholds and columns come from the
+// kernel's arguments.  The two region branches per belief diverge within a wave of mixed candidates; each side is then run once.
+// No LDS, no atomics, nothing chosen from M: a candidate's numbers are bitwise the same in any batch.
+#include <cfloat>
+
+#include "dev.h"
+
+namespace {
+constexpr int CEI_T = 64;          // threads per workgroup
+constexpr double CEI_XC = 3.0;     // the crossover: continued fraction for z < -CEI_XC
+constexpr int CEI_DEPTH = 60;      // partial quotients of T(x)
+constexpr double CEI_LOG_SQRT2PI = 0.91893853320467274178;
+constexpr double CEI_INV_SQRT2PI = 0.39894228040143267794;
+constexpr double CEI_INV_SQRT2 = 0.70710678118654752440;
+} // namespace
+
+// 1 / T(x) = x + 2 / (x + 3 / (x + ... + CEI_DEPTH / x)) for x > 0, bottom-up; x = inf: inf
+static __device__ __forceinline__ double cei_inv_T(double x)
+{
+    double t = x;
+#pragma unroll 4
+    for (int k = CEI_DEPTH; k >= 2; --k)
+        t = x + (double)k / t;
+    return t;
+}
+
+// log h(z) with Phi(z) / h(z) and phi(z) / h(z).  z = -inf: (-inf, inf, inf); z = +inf: (inf, 0, 0); NaN: NaN.
+static __device__ __forceinline__ void cei_log_h(double z, double& lh, double& r_Phi, double& r_phi)
+{
+    if (z < -CEI_XC) {
+        const double x = -z, t = cei_inv_T(x), rinv = x + 1.0 / t; // rinv = 1 / R(x)
+        lh = -0.5 * x * x - CEI_LOG_SQRT2PI - (log(rinv) + log(t));
+        r_Phi = t;
+        r_phi = rinv * t;
+        return;
+    }
+    const double a = fabs(z);
+    const double phi = exp(-0.5 * a * a) * CEI_INV_SQRT2PI;
+    const double Q = 0.5 * erfc(a * CEI_INV_SQRT2);
+    const double fm = Q == 0.0 ? phi : phi - a * Q; // h(-|z|); (inf 0 at |z| = inf)
+    const double h = z < 0.0 ? fm : z + fm;
+    const double Phi = z < 0.0 ? Q : 1.0 - Q;
+    lh = log(h);
+    r_Phi = Phi / h;
+    r_phi = phi / h;
+}
+
+// log Phi(u) with lambda(u) = phi(u) / Phi(u).  u = -inf: (-inf, inf); u = +inf: (0, 0); NaN: NaN.
+static __device__ __forceinline__ void cei_log_Phi(double u, double& lP, double& lam)
+{
+    if (u < -CEI_XC) {
+        const double x = -u, rinv = x + 1.0 / cei_inv_T(x);
+        lP = -0.5 * x * x - CEI_LOG_SQRT2PI - log(rinv);
+        lam = rinv;
+        return;
+    }
+    const double a = fabs(u);
+    const double phi = exp(-0.5 * a * a) * CEI_INV_SQRT2PI;
+    const double Q = 0.5 * erfc(a * CEI_INV_SQRT2);
+    if (u < 0.0) {
+        lP = log(Q);
+        lam = phi / Q;
+    }
+    else {
+        lP = log1p(-Q);
+        lam = phi / (1.0 - Q);
+    }
+}
+
+__global__ __launch_bounds__(CEI_T) void k_logcei(CeiArgs q)
+{
+    const int64_t m = (int64_t)blockIdx.x * CEI_T + threadIdx.x;
+    if (m >= q.M)
+        return;
+    const double ninf = __longlong_as_double(0xfff0000000000000LL);
+    const int C = q.C;
+    double sig = 0.0;
+    if (q.var) { // one model, several outputs: the shared sigma, clamped as gp.hpp:621-623
+        const double v = q.var[m];
+        sig = sqrt((v > DBL_EPSILON ? v : (v != v ? v : 0.0)) + q.var_add);
+    }
+    double total = 0.0;
+    bool any_nan = false, any_ninf = false;
+
+    if (q.with_ei || q.mu_out) {
+        double mu0 = q.mu[m + (int64_t)q.col[0] * q.ldmu];
+        if (q.add)
+            mu0 += q.add[m];
+        if (q.mu_out)
+            q.mu_out[m] = mu0;
+        double t0 = 0.0, pm = 0.0, ps = 0.0;
+        if (q.with_ei) {
+            const double s = q.var ? sig : q.sd[m];
+            const double d = mu0 - q.f_best - q.xi;
+            if (s == 0.0) { // no uncertainty: the improvement itself, or none
+                t0 = d > 0.0 ? log(d) : (d != d ? d : ninf);
+                pm = d > 0.0 ? 1.0 / d : (d != d ? d : 0.0);
+                ps = d != d ? d : 0.0;
+            }
+            else {
+                double lh, rP, rp;
+                cei_log_h(d / s, lh, rP, rp);
+                t0 = log(s) + lh;
+                pm = rP / s;
+                ps = rp / s;
+            }
+            total = t0;
+            any_nan = t0 != t0;
+            any_ninf = t0 == ninf;
+        }
+        if (q.terms)
+            q.terms[m] = t0;
+        if (q.partials) {
+            q.partials[m] = pm;
+            q.partials[m + q.ldp] = ps;
+        }
+    }
+    else {
+        if (q.terms)
+            q.terms[m] = 0.0;
+        if (q.partials)
+            q.partials[m] = q.partials[m + q.ldp] = 0.0;
+    }
+
+    for (int k = 0; k < C; ++k) {
+        double mu = q.mu[m + (int64_t)q.col[1 + k] * q.ldmu];
+        if (q.add)
+            mu += q.add[m + (int64_t)(1 + k) * q.lda];
+        if (q.mu_out)
+            q.mu_out[m + (int64_t)(1 + k) * q.ldm] = mu;
+        const double s = q.var ? sig : q.sd[m + (int64_t)(1 + k) * q.lds];
+        const double d = mu - q.thr[k];
+        double term, pm, ps;
+        if (s == 0.0) { // no uncertainty: met or not
+            term = d >= 0.0 ? 0.0 : (d != d ? d : ninf);
+            pm = ps = d != d ? d : 0.0;
+        }
+        else {
+            const double u = d / s;
+            double lam;
+            cei_log_Phi(u, term, lam);
+            pm = lam / s;
+            ps = lam == 0.0 ? 0.0 : -(u * lam) / s; // (inf 0 at u = +inf)
+        }
+        total += term;
+        any_nan |= term != term;
+        any_ninf |= term == ninf;
+        if (q.terms)
+            q.terms[m + (int64_t)(1 + k) * q.ldt] = term;
+        if (q.partials) {
+            q.partials[m + (int64_t)(2 + k) * q.ldp] = pm;
+            q.partials[m + (int64_t)(2 + C + k) * q.ldp] = ps;
+        }
+    }
+    if (total != total && !any_nan && any_ninf) // +inf (mu0 = +inf) beside -inf (a constraint surely missed): not feasible
+        total = ninf;
+    if (q.logcei)
+        q.logcei[m] = total;
+}
+
+void launch_logcei(hipStream_t s, const CeiArgs& q)
+{
+    if (q.M <= 0 || q.C < 0 || q.C > 16)
+        return;
+    GPE_LAUNCH(k_logcei, dim3((unsigned)((q.M + CEI_T - 1) / CEI_T)), dim3(CEI_T), 0, s, q);
+}

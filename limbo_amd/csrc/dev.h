@@ -562,6 +562,26 @@ struct EhviArgs {
 };
 void launch_ehvi2(hipStream_t s, const EhviArgs& q);
 
+// ---- constrained expected improvement in the log domain (cei.hip; include/gpe_cei.h) ------------------------------------
+// logcei[m] and, where asked, terms (column j at terms + j ldt, j <= C) and partials (column j at partials + j ldp, j < 2 + 2 C) of
+// candidate m < M; one thread each.  Belief j (0: the objective, 1 .. C: the constraints) of candidate m: the mean mu[m + col[j] ldmu]
+// (+ add[m + j lda]; add == null: nothing is added); var == null: the standard deviation sd[m + j lds]; otherwise every one is
+// sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  with_ei == 0: belief 0 is not read.  mu_out (may be null): the 1 + C means
+// as used, column j at mu_out + j ldm.
+struct CeiArgs {
+    int with_ei, C;
+    double f_best, xi;
+    double thr[16]; // GPE_CEI_MAX_CONSTRAINTS
+    int col[17];
+    const double *mu, *add, *sd, *var;
+    int64_t ldmu, lda, lds;
+    double var_add;
+    int64_t M;
+    double *logcei, *terms, *partials, *mu_out;
+    int64_t ldt, ldp, ldm;
+};
+void launch_logcei(hipStream_t s, const CeiArgs& q);
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);
