@@ -59,6 +59,7 @@
 #include <limbo/model/gp/kg.hpp>
 #include <limbo/model/gp/ehvi.hpp>
 #include <limbo/model/gp/cei.hpp>
+#include <limbo/model/gp/mes.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -73,6 +74,7 @@
 #include "../../../gpe_kg.h"
 #include "../../../gpe_ehvi.h"
 #include "../../../gpe_cei.h"
+#include "../../../gpe_mes.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -738,6 +740,77 @@ namespace limbo {
                 _eng.check(gpe_logcei_values(_eng.get(), with_ei, f_best, xi, (int)thr.size(), thr.data(), mu0.data(), s0.data(), mu_c.data(), s_c.data(),
                                M, logcei.data(), terms ? terms->data() : nullptr, partials ? partials->data() : nullptr),
                     "gpe_logcei_values");
+            }
+
+            /// Addition (include/gpe_mes.h, model/gp/mes.hpp): the LOG of the max-value entropy search of every candidate under the
+            /// outputs `outs` of this model (all share sigma), against K sampled maxima per output: ystar is K x outs.size()
+            /// column-major (limbo_amd::max_value_samples, acqui/mes.hpp).  One output: MES; several: MESMO, the sum over them.  The
+            /// means are k^T alpha plus the mean functor; sigma^2 is the clamped variance of the LATENT function, or, observation ==
+            /// true, with the kernel's noise added (what query() reports).  partials (may be null): M x 2 J column-major, d/d mu_j
+            /// then d/d s_j; terms (may be null): M x J, the log of each output's MES.  The model is not changed.  On the model's
+            /// home device; no samples (the prior), a host-resident model below the batch crossover and kernels without device
+            /// code: query_batch() and the host sum of the same definition.
+            void max_value_entropy(const std::vector<Eigen::VectorXd>& candidates, const std::vector<int>& outs, const std::vector<double>& ystar,
+                bool observation, std::vector<double>& logmes, std::vector<double>* terms = nullptr, std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = candidates.size();
+                const int J = (int)outs.size();
+                const int K = J > 0 ? (int)(ystar.size() / (size_t)J) : 0;
+                bool ok = J >= 1 && (size_t)K * (size_t)J == ystar.size()
+                    && gpe_mes_values(nullptr, J, K, ystar.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr) == GPE_OK;
+                for (int j = 0; ok && j < J; ++j) {
+                    ok = outs[j] >= 0 && outs[j] < _dim_out;
+                    for (int i = 0; ok && i < j; ++i)
+                        ok = outs[i] != outs[j];
+                }
+                if (!ok)
+                    throw std::invalid_argument("limbo_amd: max_value_entropy(): bad argument (include/gpe_mes.h)");
+                logmes.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign(2 * (size_t)J * (size_t)M, 0.0);
+                if (terms)
+                    terms->assign((size_t)J * (size_t)M, 0.0);
+                if (M == 0)
+                    return;
+                const double noise = _kernel_function.noise();
+                if (_joint_on_host(M)) {
+                    Eigen::MatrixXd mu;
+                    Eigen::VectorXd s2;
+                    query_batch(candidates, mu, s2);
+                    std::vector<double> mj((size_t)M * J), sj((size_t)M * J);
+                    for (int64_t m = 0; m < M; ++m)
+                        for (int j = 0; j < J; ++j) {
+                            mj[(size_t)(m + M * j)] = mu(m, outs[j]);
+                            sj[(size_t)(m + M * j)] = std::sqrt(observation ? s2(m) : std::max(s2(m) - noise, 0.0));
+                        }
+                    limbo_amd::mes_host::values(J, K, ystar.data(), mj.data(), sj.data(), M, logmes.data(), terms ? terms->data() : nullptr,
+                        partials ? partials->data() : nullptr);
+                    return;
+                }
+                const std::vector<double> Xc = _joint_points(candidates);
+                std::vector<double> add((size_t)J * (size_t)M);
+                for (int64_t m = 0; m < M; ++m) {
+                    const Eigen::VectorXd mv = _mean_function(candidates[(size_t)m], *this);
+                    for (int j = 0; j < J; ++j)
+                        add[(size_t)(M * j + m)] = mv(outs[j]);
+                }
+                _eng.check(gpe_mes_batch(_eng.get(), J, outs.data(), K, ystar.data(), Xc.data(), M, add.data(), observation ? noise : 0.0, logmes.data(),
+                               terms ? terms->data() : nullptr, partials ? partials->data() : nullptr, nullptr, nullptr),
+                    "gpe_mes_batch");
+            }
+            /// gpe_mes_values through this model's engine handle (has_engine()): beliefs the caller computed (mu, s: M x J column-major)
+            void mes_values(int J, const std::vector<double>& ystar, const std::vector<double>& mu, const std::vector<double>& s,
+                std::vector<double>& logmes, std::vector<double>* terms = nullptr, std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = J > 0 ? (int64_t)(mu.size() / (size_t)J) : 0;
+                logmes.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign(2 * (size_t)J * (size_t)M, 0.0);
+                if (terms)
+                    terms->assign((size_t)J * (size_t)M, 0.0);
+                _eng.check(gpe_mes_values(_eng.get(), J, J > 0 ? (int)(ystar.size() / (size_t)J) : 0, ystar.data(), mu.data(), s.data(), M, logmes.data(),
+                               terms ? terms->data() : nullptr, partials ? partials->data() : nullptr),
+                    "gpe_mes_values");
             }
 
             /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise

@@ -26,6 +26,7 @@ REMOVE_HOW = {"auto": 0, "update": 1, "recompute": 2}
 KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 EHVI_MAX_FRONT = 2048  # include/gpe_ehvi.h: GPE_EHVI_MAX_FRONT
 CEI_MAX_CONSTRAINTS = 16  # include/gpe_cei.h: GPE_CEI_MAX_CONSTRAINTS
+MES_MAX_OUTPUTS, MES_MAX_SAMPLES = 8, 1024  # include/gpe_mes.h: GPE_MES_MAX_OUTPUTS, GPE_MES_MAX_SAMPLES
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -171,6 +172,10 @@ def _sig(lib, prefix):
             "logcei_batch": [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp, _i64, _dp, C.c_double,
                              _dp, _dp, _dp, _dp, _dp],
             "cei_phase_ms": [_vp, _dp],
+            # include/gpe_mes.h: max-value entropy search in the log domain
+            "mes_values": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _dp],
+            "mes_batch": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, _i64, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp],
+            "mes_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -657,6 +662,55 @@ class Handle:
         """{solves, kernel, readback} of the last logcei_batch call in ms (set_profiling(True) first)."""
         ms = np.zeros(3)
         self._chk(self.lib.fn("cei_phase_ms")(self._h, _d(ms)), "cei_phase_ms")
+        return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
+
+    # -- max-value entropy search in the log domain (include/gpe_mes.h; HIP library only)
+    def mes_values(self, ystar, mu, s, want=("terms", "partials"), check=True):
+        """The kernel alone on host-supplied beliefs (s: standard deviations): ystar (K, J) sampled maxima, mu and s (M, J).  Any
+        handle serves.  Returns (status, logmes (M), terms (M, J) or None, partials (M, 2 J) or None: d/d mu_j, then d/d s_j).
+        check=False hands a negative GPE_ERR_* back instead of raising."""
+        ys = np.asarray(ystar, dtype=np.float64)
+        ys = _c(ys.reshape(ys.shape[0], -1), "F")
+        K, J = ys.shape
+        m_, s_ = (_c(np.asarray(v, dtype=np.float64).reshape(-1, J), "F") for v in (mu, s))
+        M = m_.shape[0]
+        assert s_.shape[0] == M
+        val = np.zeros(M)
+        terms = np.zeros((M, J), order="F") if "terms" in want else None
+        part = np.zeros((M, 2 * J), order="F") if "partials" in want else None
+        opt = lambda a: _d(a) if a is not None and a.size else None
+        rc = self.lib.fn("mes_values")(self._h, J, K, _d(ys), opt(m_), opt(s_), M, opt(val), opt(terms), opt(part))
+        if check:
+            self._chk(rc, "mes_values")
+        return rc, val, terms, part
+
+    def mes_batch(self, Xc, ystar, outs=None, mean_add=None, var_add=0.0, want=("logmes", "terms", "partials", "mu", "var"), check=True):
+        """The log max-value entropy search of every row of Xc under the handle's outputs `outs` (default: all), which share sigma,
+        against the sampled maxima ystar (K, J).  mean_add: (M, J) added to k^T alpha, or None; var_add: added to the clamped
+        variance (0: the latent function).  Returns (status, logmes (M), terms (M, J), partials (M, 2 J), mu (M, J), var (M)), None
+        for what `want` leaves out."""
+        Xc = _c(Xc).reshape(-1, self.D)
+        M = Xc.shape[0]
+        ys = np.asarray(ystar, dtype=np.float64)
+        ys = _c(ys.reshape(ys.shape[0], -1), "F")
+        K, J = ys.shape
+        o = np.ascontiguousarray(np.asarray(range(J) if outs is None else outs, dtype=np.int32).reshape(-1))
+        assert o.shape[0] == J
+        ma = _c(np.asarray(mean_add, dtype=np.float64).reshape(M, J), "F") if mean_add is not None else None
+        names = ("logmes", "terms", "partials", "mu", "var")
+        out = {"logmes": np.zeros(M), "terms": np.zeros((M, J), order="F"), "partials": np.zeros((M, 2 * J), order="F"),
+               "mu": np.zeros((M, J), order="F"), "var": np.zeros(M)}
+        ptr = [_d(out[k]) if k in want else None for k in names]
+        rc = self.lib.fn("mes_batch")(self._h, J, o.ctypes.data_as(C.POINTER(C.c_int)), K, _d(ys), _d(Xc), M,
+                                      _d(ma) if ma is not None else None, float(var_add), *ptr)
+        if check:
+            self._chk(rc, "mes_batch")
+        return (rc,) + tuple(out[k] if k in want else None for k in names)
+
+    def mes_phase_ms(self):
+        """{solves, kernel, readback} of the last mes_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("mes_phase_ms")(self._h, _d(ms)), "mes_phase_ms")
         return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
 
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)

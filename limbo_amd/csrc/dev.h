@@ -582,6 +582,25 @@ struct CeiArgs {
 };
 void launch_logcei(hipStream_t s, const CeiArgs& q);
 
+// ---- max-value entropy search in the log domain (mes.hip; include/gpe_mes.h) --------------------------------------------
+// logmes[m] and, where asked, terms (column j at terms + j ldt, j < J) and partials (d/d mu_j at partials + j ldp, d/d s_j at
+// partials + (J + j) ldp) of candidate m < M; one wave each.  ystar: K x J column-major on the device, finite.  Belief j of candidate
+// m: the mean mu[m + col[j] ldmu] (+ add[m + j lda]; add == null: nothing is added); var == null: the standard deviation
+// sd[m + j lds]; otherwise every one is sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  mu_out (may be null): the J means as
+// used, column j at mu_out + j ldm.
+struct MesArgs {
+    int J, K;
+    int col[8]; // GPE_MES_MAX_OUTPUTS
+    const double* ystar;
+    const double *mu, *add, *sd, *var;
+    int64_t ldmu, lda, lds;
+    double var_add;
+    int64_t M;
+    double *logmes, *terms, *partials, *mu_out;
+    int64_t ldt, ldp, ldm;
+};
+void launch_mes(hipStream_t s, const MesArgs& q);
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);

@@ -1,0 +1,151 @@
+"""The reference of the max-value-entropy-search tests (tests/test_mes_host.py, tests/test_gpu_mes.py): never the engine.
+
+ref_mes(ystar, mu, s)      include/gpe_mes.h in numpy / scipy for all candidates at once: ystar (K, J), mu and s (M, J) ->
+                           (logmes (M), terms (M, J), partials (M, 2 J): d/d mu_0 .. mu_{J-1}, then d/d s_0 .. s_{J-1}).
+log_t(g)                   (log t(g), t'(g) / t(g)) of the per-sample term t(g) = g phi(g) / (2 Phi(g)) - log Phi(g), elementwise.
+mp_mes(ystar, mu, s)       the same as ref_mes for ONE candidate in >= 60-digit arithmetic (mpmath), from the definition itself; the
+                           positive tail of log Phi through log1p(-Phi(-g)).  What ref_mes's own error is measured against.
+textbook_t(g)              t(g) as written, in double: NaN below g = -38.5, exactly 0 above g = +38.6.
+err(got, truth)            |got - truth| / max(1, |truth|): the measure of every comparison; equal infinities count as 0.
+
+Three regions (x = |g|, R(x) = Phi(-x) / phi(x), 1 / T = x + c2, c2 = 2 / (x + 3 / (x + ...)), lambda = phi / Phi):
+  g < -CROSSOVER    lambda = x + T,  t = log sqrt(2 pi) + log(x + T) - x T / 2,  t' = -(lambda / 2) c2 T
+  g > +CROSSOVER    Q = phi R,  log t = -g^2 / 2 - log sqrt(2 pi) + log B,  B = g / (2 (1 - Q)) + R (-log1p(-Q) / Q),
+                    t' / t = -[1 + g (g + phi / (1 - Q))] / (2 (1 - Q) B)
+  otherwise         t = g lambda / 2 - log Phi,  t' = -(lambda / 2) (1 + g (g + lambda))
+The continued fraction is taken to a depth far beyond need (REF_DEPTH); the kernel's is 60 (limbo_amd/csrc/mes.hip: MES_DEPTH)."""
+import math
+
+import numpy as np
+from scipy.special import erfc, log_ndtr
+
+SQRT2, SQRT2PI, LOG_SQRT2PI = math.sqrt(2.0), math.sqrt(2.0 * math.pi), 0.5 * math.log(2.0 * math.pi)
+CROSSOVER = 3.0  # the kernel's (limbo_amd/csrc/mes.hip: MES_XC); the tests probe both sides of it
+REF_DEPTH = 400
+MAX_OUTPUTS = 8
+MAX_SAMPLES = 1024
+
+
+def err(got, truth):
+    got, truth = np.asarray(got, dtype=float), np.asarray(truth, dtype=float)
+    with np.errstate(invalid="ignore"):
+        e = np.abs(got - truth) / np.maximum(1.0, np.abs(truth))
+    same = (got == truth) | (np.isnan(got) & np.isnan(truth))
+    return np.where(same, 0.0, np.where(np.isnan(e), np.inf, e))
+
+
+def _c2(x, depth=REF_DEPTH):
+    """c2(x) = 2 / (x + 3 / (x + ...)) for x > 0, bottom-up: 1 / T = x + c2"""
+    t = x.copy()
+    for k in range(depth, 2, -1):
+        t = x + k / t
+    return 2.0 / t
+
+
+def log_t(g):
+    g = np.asarray(g, dtype=float)
+    lo, hi = g < -CROSSOVER, g > CROSSOVER
+    with np.errstate(all="ignore"):
+        x = np.where(lo | hi, np.abs(g), CROSSOVER + 1.0)
+        c2 = _c2(x)
+        T = 1.0 / (x + c2)
+        # below
+        lam = x + T
+        t_lo = LOG_SQRT2PI + np.log(lam) - 0.5 * x * T
+        lt_lo, r_lo = np.log(t_lo), -(0.5 * lam) * c2 * T / t_lo
+        # above
+        phi = np.exp(-0.5 * x * x) / SQRT2PI
+        R = 1.0 / (x + T)
+        Q = phi * R
+        quot = np.where(Q > 0, -np.log1p(-Q) / np.where(Q > 0, Q, 1.0), 1.0)
+        B = x / (2.0 * (1.0 - Q)) + R * quot
+        lt_hi = -0.5 * x * x - LOG_SQRT2PI + np.log(B)
+        r_hi = -(1.0 + x * (x + phi / (1.0 - Q))) / (2.0 * (1.0 - Q) * B)
+        # between
+        m = np.where(lo | hi, 0.0, g)
+        lP = log_ndtr(m)
+        lm = np.exp(-0.5 * m * m - lP) / SQRT2PI
+        t_mid = 0.5 * m * lm - lP
+        lt_mid, r_mid = np.log(t_mid), -(0.5 * lm) * (1.0 + m * (m + lm)) / t_mid
+        lt = np.where(lo, lt_lo, np.where(hi, lt_hi, lt_mid))
+        r = np.where(lo, r_lo, np.where(hi, r_hi, r_mid))
+        lt = np.where(g == np.inf, -np.inf, np.where(g == -np.inf, np.inf, lt))
+        r = np.where(np.isinf(g), 0.0, r)
+    return lt, r
+
+
+def _lse(a, axis):
+    """(log sum exp, weights) along axis, the maximum taken first; all -inf: (-inf, 0); a +inf: (+inf, 0)"""
+    with np.errstate(all="ignore"):
+        L = np.max(a, axis=axis, keepdims=True)
+        fin = np.isfinite(L)
+        e = np.exp(np.where(fin, a - np.where(fin, L, 0.0), -np.inf))
+        S = e.sum(axis=axis, keepdims=True)
+        w = np.where(fin, e / np.where(fin, S, 1.0), 0.0)
+        v = np.where(fin, L + np.log(np.where(fin, S, 1.0)), L)
+    return np.squeeze(v, axis=axis), w
+
+
+def ref_mes(ystar, mu, s):
+    ystar = np.asarray(ystar, dtype=float)
+    ystar = ystar.reshape(ystar.shape[0], -1)
+    K, J = ystar.shape
+    mu, s = np.asarray(mu, dtype=float).reshape(-1, J), np.asarray(s, dtype=float).reshape(-1, J)
+    M = mu.shape[0]
+    with np.errstate(all="ignore"):
+        pos = s > 0
+        sp = np.where(pos, s, 1.0)
+        g = (ystar.T[None, :, :] - mu[:, :, None]) / sp[:, :, None]  # (M, J, K)
+        lt, r = log_t(g)
+        lk, w = _lse(lt, 2)
+        terms = np.where(pos, lk - math.log(K), -np.inf)
+        dm = np.where(pos, -(w * r).sum(axis=2) / sp, 0.0)
+        ds = np.where(pos, -(w * np.where(r == 0.0, 0.0, g * r)).sum(axis=2) / sp, 0.0)
+        val, W = _lse(terms, 1)
+        part = np.concatenate([W * dm, W * ds], axis=1)
+        bad = np.isnan(mu).any(axis=1) | np.isnan(s).any(axis=1) | np.isnan(terms).any(axis=1)
+        val = np.where(bad, np.nan, val)
+        terms = np.where(bad[:, None], np.nan, terms)
+        part = np.where(bad[:, None], np.nan, part)
+    return val, terms, part
+
+
+def textbook_t(g):
+    """t as written: g phi / (2 Phi) - log Phi with Phi = erfc(-g / sqrt 2) / 2"""
+    g = np.asarray(g, dtype=float)
+    with np.errstate(all="ignore"):
+        phi = np.exp(-0.5 * g * g) / SQRT2PI
+        Phi = 0.5 * erfc(-g / SQRT2)
+        return g * phi / (2.0 * Phi) - np.log(Phi)
+
+
+def mp_mes(ystar, mu, s, dps=60):
+    """one candidate, s > 0 throughout: (logmes, [terms], [d/d mu_j] + [d/d s_j]) as mpf"""
+    import mpmath as mp
+
+    ystar = np.asarray(ystar, dtype=float)
+    ystar = ystar.reshape(ystar.shape[0], -1)
+    K, J = ystar.shape
+    mu, s = np.asarray(mu, dtype=float).reshape(-1), np.asarray(s, dtype=float).reshape(-1)
+    gmax = max(1.0, float(np.max(np.abs((ystar - mu[None, :]) / s[None, :]))))
+    with mp.workdps(dps + int(2 * math.log10(gmax)) + 5):
+        terms, dm, ds = [], [], []
+        for j in range(J):
+            mj, sj = mp.mpf(float(mu[j])), mp.mpf(float(s[j]))
+            ts, dts, gs = [], [], []
+            for k in range(K):
+                g = (mp.mpf(float(ystar[k, j])) - mj) / sj
+                Phi = mp.ncdf(g)
+                lP = mp.log1p(-mp.ncdf(-g)) if g > 0 else mp.log(Phi)
+                lam = mp.npdf(g) / Phi
+                ts.append(g * lam / 2 - lP)
+                dts.append(-(lam / 2) * (1 + g * (g + lam)))
+                gs.append(g)
+            tot = mp.fsum(ts)
+            terms.append(mp.log(tot / K))
+            dm.append(-mp.fsum(dts) / (tot * sj))
+            ds.append(-mp.fsum(a * b for a, b in zip(gs, dts)) / (tot * sj))
+        top = max(terms)
+        val = top + mp.log(mp.fsum(mp.exp(t - top) for t in terms))
+        W = [mp.exp(t - val) for t in terms]
+        return val, terms, [w * d for w, d in zip(W, dm)] + [w * d for w, d in zip(W, ds)]
