@@ -1,0 +1,171 @@
+// limbo/acqui/nei.hpp — noisy expected improvement in the log domain (Letham, Karrer, Ottoni, Bakshy 2019; include/gpe_nei.h,
+// model::GP::log_noisy_ei).
+// Not in the reference: its EI (src/limbo/acqui/ei.hpp:77-120) takes the incumbent f+ from the caller, in practice the largest NOISY
+// observation, which is biased upwards.  Noisy EI averages EI over joint posterior draws of the function at baseline points: every
+// draw has its own incumbent and the belief at the candidate is conditioned on that draw.  Conditioning leaves little variance near
+// the baseline, the plain value is exactly 0 over most of the box, so the value here is the logarithm.  Value only: the gradient in
+// the point needs d c_x / d x, a B x D block per candidate; opt::BatchGradSearch does not take LogNEI.
+#ifndef LIMBO_AMD_ACQUI_NEI_HPP
+#define LIMBO_AMD_ACQUI_NEI_HPP
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <stdexcept>
+#include <vector>
+
+#include <Eigen/Core>
+
+#include <limbo/opt/optimizer.hpp>
+
+#include "../../../gpe_nei.h"
+
+namespace limbo_amd {
+    /// The baseline of noisy EI, pruned: the training points that are the arg-max of at least one of S_prune joint posterior draws
+    /// of output `out` over the training inputs (GP::sample_argmax, in chunks of at most GP::joint_max_points() points — a draw's
+    /// arg-max is then the chunk winner with the largest value), and always the training point with the largest posterior mean.
+    /// A model of 16 384 samples then conditions on a few dozen points instead of on all of them.  Base normals from
+    /// std::mt19937_64(seed) (+ the chunk's number): a deterministic function of (model, S_prune, seed, jitter).  Returns ascending
+    /// indices into model.samples().
+    template <typename Model>
+    std::vector<int64_t> nei_baseline_indices(const Model& model, int S_prune, uint64_t seed, double jitter = 1e-6, int out = 0)
+    {
+        const std::vector<Eigen::VectorXd>& X = model.samples();
+        const int64_t n = (int64_t)X.size();
+        const int P = (int)model.dim_out();
+        std::vector<int64_t> keep;
+        if (n == 0)
+            return keep;
+        if (S_prune < 0 || out < 0 || out >= P)
+            throw std::invalid_argument("limbo_amd: nei_baseline(): bad argument");
+        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, model.joint_max_points()));
+        std::vector<int64_t> win((size_t)S_prune, -1);
+        std::vector<double> top((size_t)S_prune, 0.0);
+        for (int64_t c0 = 0, ci = 0; c0 < n && S_prune > 0; c0 += chunk, ++ci) {
+            const std::vector<Eigen::VectorXd> pts(X.begin() + c0, X.begin() + std::min(n, c0 + chunk));
+            const std::vector<double> Z = Model::standard_normals(pts.size() * (size_t)S_prune * (size_t)P, seed + (uint64_t)ci);
+            std::vector<int64_t> am;
+            std::vector<double> fm;
+            model.sample_argmax(pts, Z, S_prune, jitter, am, fm);
+            for (int s = 0; s < S_prune; ++s) {
+                const size_t q = (size_t)(s + S_prune * out);
+                if (win[(size_t)s] < 0 || fm[q] > top[(size_t)s]) {
+                    win[(size_t)s] = c0 + am[q];
+                    top[(size_t)s] = fm[q];
+                }
+            }
+        }
+        keep.assign(win.begin(), win.end());
+        // the largest posterior mean over the training inputs (the lowest index on ties)
+        Eigen::MatrixXd mu;
+        Eigen::VectorXd s2;
+        model.query_batch(X, mu, s2);
+        int64_t best = 0;
+        for (int64_t i = 1; i < n; ++i)
+            if (mu(i, out) > mu(best, out))
+                best = i;
+        keep.push_back(best);
+        std::sort(keep.begin(), keep.end());
+        keep.erase(std::unique(keep.begin(), keep.end()), keep.end());
+        if ((int64_t)keep.size() > GPE_NEI_MAX_BASELINE) // (more winners than the call takes: the first ones, the best mean among them)
+        {
+            keep.resize(GPE_NEI_MAX_BASELINE);
+            if (!std::binary_search(keep.begin(), keep.end(), best)) {
+                keep.back() = best;
+                std::sort(keep.begin(), keep.end());
+            }
+        }
+        return keep;
+    }
+    /// ... as points
+    template <typename Model>
+    std::vector<Eigen::VectorXd> nei_baseline(const Model& model, int S_prune, uint64_t seed, double jitter = 1e-6, int out = 0)
+    {
+        std::vector<Eigen::VectorXd> pts;
+        for (int64_t i : nei_baseline_indices(model, S_prune, seed, jitter, out))
+            pts.push_back(model.samples()[(size_t)i]);
+        return pts;
+    }
+
+    /// lognei[m] of every candidate under output `out`: S draws over `baseline` with base normals from std::mt19937_64(seed).
+    /// Throws std::runtime_error when the baseline's covariance + jitter I is not positive definite.
+    template <typename Params, typename Model>
+    std::vector<double> lognei_batch(const Model& model, const std::vector<Eigen::VectorXd>& candidates, const std::vector<Eigen::VectorXd>& baseline,
+        int S, uint64_t seed, double jitter = 1e-6, double xi = 0.0, int out = 0)
+    {
+        std::vector<double> v;
+        if (candidates.empty())
+            return v;
+        const std::vector<double> Z = Model::standard_normals(baseline.size() * (size_t)std::max(S, 0), seed);
+        const int rc = model.log_noisy_ei(candidates, baseline, Z, out, jitter, xi, v);
+        if (rc > 0)
+            throw std::runtime_error("limbo_amd: lognei_batch(): the baseline's covariance + jitter I is not positive definite (pivot "
+                + std::to_string(rc) + "): raise jitter");
+        return v;
+    }
+    /// the index of the largest value (the lowest one on exact ties; NaN never wins), -1 without candidates
+    inline int64_t lognei_best(const std::vector<double>& v)
+    {
+        int64_t best = -1;
+        for (size_t m = 0; m < v.size(); ++m)
+            if (best < 0 || v[m] > v[(size_t)best])
+                best = (int64_t)m;
+        return best;
+    }
+    template <typename Params, typename Model>
+    int64_t lognei_best(const Model& model, const std::vector<Eigen::VectorXd>& candidates, const std::vector<Eigen::VectorXd>& baseline, int S,
+        uint64_t seed, double jitter = 1e-6, double xi = 0.0, int out = 0)
+    {
+        return lognei_best(lognei_batch<Params>(model, candidates, baseline, S, seed, jitter, xi, out));
+    }
+} // namespace limbo_amd
+
+namespace limbo {
+    namespace acqui {
+        /// The acquisition object over one model: output 0 is the objective.  The baseline is given, or pruned at construction by
+        /// limbo_amd::nei_baseline; the base normals are drawn once, at construction, so that every call scores against the same
+        /// draws (common random numbers: the landscape is a deterministic function of the point).  The aggregator is not applied:
+        /// the output itself is scored.  Value only (operator() with gradient == true throws): opt::make_batch_objective takes the
+        /// object through batch(); opt::BatchGradSearch does not take it.
+        template <typename Params, typename Model>
+        class LogNEI {
+        public:
+            LogNEI(const Model& model, const std::vector<Eigen::VectorXd>& baseline, int S, uint64_t seed, double jitter = 1e-6, double xi = 0.0)
+                : _m(model), _baseline(baseline), _Z(Model::standard_normals(baseline.size() * (size_t)std::max(S, 0), seed)), _jitter(jitter), _xi(xi)
+            {
+                if (_baseline.empty() || S < 1)
+                    throw std::invalid_argument("limbo_amd: acqui::LogNEI: a baseline and S >= 1 draws are needed");
+            }
+            LogNEI(const Model& model, int S, uint64_t seed, int S_prune = 64, double jitter = 1e-6, double xi = 0.0)
+                : LogNEI(model, limbo_amd::nei_baseline(model, S_prune, seed + 1, jitter), S, seed, jitter, xi) {}
+            size_t dim_in() const { return _m.dim_in(); }
+            size_t dim_out() const { return _m.dim_out(); }
+            const std::vector<Eigen::VectorXd>& baseline() const { return _baseline; }
+
+            template <typename AggregatorFunction>
+            std::vector<double> batch(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction&) const
+            {
+                std::vector<double> v;
+                if (points.empty())
+                    return v;
+                const int rc = _m.log_noisy_ei(points, _baseline, _Z, 0, _jitter, _xi, v);
+                if (rc > 0)
+                    throw std::runtime_error("limbo_amd: acqui::LogNEI: the baseline's covariance + jitter I is not positive definite: raise jitter");
+                return v;
+            }
+            template <typename AggregatorFunction>
+            opt::eval_t operator()(const Eigen::VectorXd& v, const AggregatorFunction& afun, bool gradient) const
+            {
+                if (gradient)
+                    throw std::logic_error("limbo_amd: acqui::LogNEI is value-only");
+                return opt::no_grad(batch(std::vector<Eigen::VectorXd>(1, v), afun)[0]);
+            }
+
+        protected:
+            const Model& _m;
+            std::vector<Eigen::VectorXd> _baseline;
+            std::vector<double> _Z;
+            double _jitter, _xi;
+        };
+    } // namespace acqui
+} // namespace limbo
+#endif

@@ -60,6 +60,7 @@
 #include <limbo/model/gp/ehvi.hpp>
 #include <limbo/model/gp/cei.hpp>
 #include <limbo/model/gp/mes.hpp>
+#include <limbo/model/gp/nei.hpp>
 #include <limbo/model/gp/kernel_lf_opt.hpp>
 #include <limbo/model/gp/no_lf_opt.hpp>
 #include <limbo/tools/math.hpp>
@@ -75,6 +76,7 @@
 #include "../../../gpe_ehvi.h"
 #include "../../../gpe_cei.h"
 #include "../../../gpe_mes.h"
+#include "../../../gpe_nei.h"
 
 namespace limbo_amd {
     /// RAII owner of one engine handle (one GP resident on the device)
@@ -811,6 +813,61 @@ namespace limbo {
                 _eng.check(gpe_mes_values(_eng.get(), J, J > 0 ? (int)(ystar.size() / (size_t)J) : 0, ystar.data(), mu.data(), s.data(), M, logmes.data(),
                                terms ? terms->data() : nullptr, partials ? partials->data() : nullptr),
                     "gpe_mes_values");
+            }
+
+            /// Addition: the largest number of points one sample() / sample_argmax() / query_joint() call takes (gpe_joint_max_points);
+            /// no bound for a model that lives on the host
+            int64_t joint_max_points() const
+            {
+                if (_samples.size() == 0 || _host_mode || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K)
+                    return std::numeric_limits<int64_t>::max();
+                int64_t m = 0;
+                _eng.check(gpe_joint_max_points(_eng.get(), &m), "gpe_joint_max_points");
+                return m;
+            }
+
+            /// Addition (include/gpe_nei.h, model/gp/nei.hpp): the LOG of the noisy expected improvement of every candidate under
+            /// output `out` (maximised): EI averaged over S joint posterior draws of the function at the `baseline` points, every
+            /// draw with its own incumbent and the belief at the candidate conditioned on it — no incumbent taken from noisy
+            /// observations.  Z: baseline.size() x S standard normals, column-major, the caller's (standard_normals()); jitter is
+            /// added to the baseline's covariance (no hidden default; 1e-6 is the usual choice).  The means are k^T alpha plus
+            /// the mean functor.  fplus (S), cvar (M, no clamp) and cmean (S x M column-major) may be null.  Returns 0, or the
+            /// 1-based first non-positive pivot of the baseline's covariance — lognei is then all zero: raise jitter.  The model is
+            /// not changed.  On the model's home device; no samples (the prior), a host-resident model below the batch crossover
+            /// and kernels without device code: the same formulas on the host (nei_host), the candidates in chunks.
+            int log_noisy_ei(const std::vector<Eigen::VectorXd>& candidates, const std::vector<Eigen::VectorXd>& baseline, const std::vector<double>& Z,
+                int out, double jitter, double xi, std::vector<double>& lognei, std::vector<double>* fplus = nullptr,
+                std::vector<double>* cvar = nullptr, std::vector<double>* cmean = nullptr) const
+            {
+                const int64_t M = candidates.size(), B = baseline.size();
+                const int S = B > 0 ? (int)(Z.size() / (size_t)B) : 0;
+                bool ok = B >= 1 && B <= GPE_NEI_MAX_BASELINE && S >= 1 && S <= GPE_NEI_MAX_SAMPLES && (size_t)S * (size_t)B == Z.size() && out >= 0
+                    && out < _dim_out && jitter >= 0.0 && std::isfinite(jitter) && std::isfinite(xi);
+                for (size_t i = 0; ok && i < Z.size(); ++i)
+                    ok = std::isfinite(Z[i]);
+                if (!ok)
+                    throw std::invalid_argument("limbo_amd: log_noisy_ei(): bad argument (include/gpe_nei.h)");
+                lognei.assign((size_t)M, 0.0);
+                if (fplus)
+                    fplus->assign((size_t)S, 0.0);
+                if (cvar)
+                    cvar->assign((size_t)M, 0.0);
+                if (cmean)
+                    cmean->assign((size_t)S * (size_t)M, 0.0);
+                if (M == 0)
+                    return 0;
+                auto ptr = [](std::vector<double>* v) { return v ? v->data() : nullptr; };
+                if (_joint_on_host(B + M))
+                    return _host_noisy_ei(candidates, baseline, Z, S, out, jitter, xi, lognei.data(), ptr(fplus), ptr(cvar), ptr(cmean));
+                const std::vector<double> Xb = _joint_points(baseline), Xc = _joint_points(candidates);
+                std::vector<double> mb((size_t)B), ma((size_t)M);
+                for (int64_t i = 0; i < B; ++i)
+                    mb[(size_t)i] = _mean_function(baseline[(size_t)i], *this)(out);
+                for (int64_t m = 0; m < M; ++m)
+                    ma[(size_t)m] = _mean_function(candidates[(size_t)m], *this)(out);
+                return _eng.check(gpe_lognei_batch(_eng.get(), out, Xb.data(), B, mb.data(), jitter, Z.data(), S, xi, Xc.data(), M, ma.data(),
+                                      lognei.data(), ptr(fplus), nullptr, nullptr, ptr(cvar), ptr(cmean), S),
+                    "gpe_lognei_batch");
             }
 
             /// Addition (include/gpe_pathwise.h, model/gp/pathwise.hpp): n_draws posterior draws per output as FUNCTIONS — pathwise
@@ -1848,6 +1905,66 @@ namespace limbo {
                         if (a != b)
                             cov[b + M * a] = cov[a + M * b];
                     }
+            }
+            // log_noisy_ei on the host: the baseline's covariance (B x B) and factor once, then the candidates in chunks of 512 — their
+            // variances and the B x chunk cross-covariance alone, never the joint covariance of all B + M points.  No samples: the prior.
+            int _host_noisy_ei(const std::vector<Eigen::VectorXd>& cand, const std::vector<Eigen::VectorXd>& base, const std::vector<double>& Z, int S,
+                int out, double jitter, double xi, double* lognei, double* fplus, double* cvar, double* cmean) const
+            {
+                const int64_t M = cand.size(), B = base.size(), n = _samples.size();
+                const double* al = n > 0 ? alpha().data() : nullptr;
+                const double* L = n > 0 ? matrixL().data() : nullptr;
+                // zs = L^-1 k(X, pts) (n x m) in place, mu[m] = k^T alpha_out + the mean functor, var (may be null) = k(v, v) - |z|^2
+                auto solve = [&](const std::vector<Eigen::VectorXd>& pts, int64_t p0, int64_t m, std::vector<double>& zs, double* mu, double* var) {
+                    zs.assign((size_t)(n * m), 0.0);
+                    for (int64_t q = 0; q < m; ++q) {
+                        const Eigen::VectorXd& v = pts[(size_t)(p0 + q)];
+                        double s = 0.0;
+                        for (int64_t i = 0; i < n; ++i) {
+                            zs[(size_t)(i + n * q)] = _kernel_function(_samples[i], v);
+                            s += zs[(size_t)(i + n * q)] * al[i + n * out];
+                        }
+                        mu[q] = s + _mean_function(v, *this)(out);
+                    }
+                    if (n > 0)
+                        limbo_amd::host_small::solve_lower(L, n, n, zs.data(), m, n);
+                    for (int64_t q = 0; q < m && var; ++q) {
+                        double zz = 0.0;
+                        for (int64_t i = 0; i < n; ++i)
+                            zz += zs[(size_t)(i + n * q)] * zs[(size_t)(i + n * q)];
+                        var[q] = _kernel_function(pts[(size_t)(p0 + q)], pts[(size_t)(p0 + q)]) - zz;
+                    }
+                };
+                std::vector<double> zb, zc, mu_b((size_t)B), Sig((size_t)(B * B));
+                solve(base, 0, B, zb, mu_b.data(), nullptr);
+                for (int64_t b = 0; b < B; ++b)
+                    for (int64_t a = b; a < B; ++a) {
+                        double s = 0.0;
+                        for (int64_t i = 0; i < n; ++i)
+                            s += zb[(size_t)(i + n * a)] * zb[(size_t)(i + n * b)];
+                        Sig[(size_t)(a + B * b)] = Sig[(size_t)(b + B * a)] = _kernel_function(base[(size_t)a], base[(size_t)b]) - s;
+                    }
+                limbo_amd::nei_host::Baseline bl;
+                if (const int rc = limbo_amd::nei_host::prepare(Sig.data(), mu_b.data(), B, jitter, Z.data(), S, bl))
+                    return rc;
+                if (fplus)
+                    std::copy(bl.fplus.begin(), bl.fplus.end(), fplus);
+                const int64_t chunk = 512;
+                std::vector<double> C((size_t)(B * std::min(chunk, M))), mu((size_t)std::min(chunk, M)), var((size_t)std::min(chunk, M));
+                for (int64_t m0 = 0; m0 < M; m0 += chunk) {
+                    const int64_t m = std::min(chunk, M - m0);
+                    solve(cand, m0, m, zc, mu.data(), var.data());
+                    for (int64_t q = 0; q < m; ++q)
+                        for (int64_t b = 0; b < B; ++b) {
+                            double s = 0.0;
+                            for (int64_t i = 0; i < n; ++i)
+                                s += zb[(size_t)(i + n * b)] * zc[(size_t)(i + n * q)];
+                            C[(size_t)(b + B * q)] = _kernel_function(base[(size_t)b], cand[(size_t)(m0 + q)]) - s;
+                        }
+                    limbo_amd::nei_host::condition(bl, Z.data(), xi, C.data(), var.data(), mu.data(), m, lognei + m0, cvar ? cvar + m0 : nullptr,
+                        cmean ? cmean + (int64_t)S * m0 : nullptr);
+                }
+                return 0;
             }
             // gpe_query_batch_grad's four outputs on the host, from matrixL() and alpha() and the kernel's derivative by (kind, log-theta)
             void _host_query_grad(const std::vector<Eigen::VectorXd>& pts, double* kta, double* var, double* dkta, double* dvar) const

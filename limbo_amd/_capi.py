@@ -27,6 +27,7 @@ KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 EHVI_MAX_FRONT = 2048  # include/gpe_ehvi.h: GPE_EHVI_MAX_FRONT
 CEI_MAX_CONSTRAINTS = 16  # include/gpe_cei.h: GPE_CEI_MAX_CONSTRAINTS
 MES_MAX_OUTPUTS, MES_MAX_SAMPLES = 8, 1024  # include/gpe_mes.h: GPE_MES_MAX_OUTPUTS, GPE_MES_MAX_SAMPLES
+NEI_MAX_BASELINE, NEI_MAX_SAMPLES = 1024, 1024  # include/gpe_nei.h: GPE_NEI_MAX_BASELINE, GPE_NEI_MAX_SAMPLES
 
 PH_KERNEL_BUILD, PH_POTRF_PANEL, PH_POTRF_UPDATE, PH_SOLVE, PH_LOGLIK, PH_INV, PH_GRAD, PH_QUERY, PH_POTRF_TALL, PH_POTRF_TAIL = range(10)
 PH_COUNT = 10
@@ -176,6 +177,11 @@ def _sig(lib, prefix):
             "mes_values": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _i64, _dp, _dp, _dp],
             "mes_batch": [_vp, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _dp, _i64, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp],
             "mes_phase_ms": [_vp, _dp],
+            # include/gpe_nei.h: noisy expected improvement in the log domain
+            "lognei_values": [_vp, C.c_int, _dp, C.c_double, _dp, _i64, _dp, _i64, _dp, _dp],
+            "lognei_batch": [_vp, C.c_int, _dp, _i64, _dp, C.c_double, _dp, C.c_int, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _dp,
+                             _dp, _i64],
+            "nei_phase_ms": [_vp, _dp],
         }
         for name, args in G.items():
             f = getattr(lib, prefix + name)
@@ -712,6 +718,60 @@ class Handle:
         ms = np.zeros(3)
         self._chk(self.lib.fn("mes_phase_ms")(self._h, _d(ms)), "mes_phase_ms")
         return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
+
+    # -- noisy expected improvement in the log domain (include/gpe_nei.h; HIP library only)
+    def lognei_values(self, fplus, cmean, csd, xi=0.0, want=("terms",), check=True):
+        """The kernel alone on host-supplied conditional beliefs: fplus (S) the draws' incumbents, cmean (S, M) the mean at
+        candidate m given draw s — any array whose columns are contiguous, what lies behind row S of a wider one is not read — and csd
+        (M) standard deviations.  Any handle serves.  Returns (status, lognei (M), terms (S, M) or None).  check=False hands a negative
+        GPE_ERR_* back instead of raising."""
+        fp = _c(np.asarray(fplus, dtype=np.float64).reshape(-1))
+        S = fp.shape[0]
+        cm = np.asarray(cmean, dtype=np.float64)
+        if cm.ndim != 2 or cm.strides[0] != 8 or (cm.shape[1] > 1 and cm.strides[1] % 8):
+            cm = _c(cm.reshape(S, -1), "F")
+        M = cm.shape[1]
+        ldm = cm.strides[1] // 8 if M > 1 else max(cm.shape[0], 1)
+        cm_ptr = C.cast(cm.ctypes.data, _dp) if cm.size else None
+        sd = _c(np.asarray(csd, dtype=np.float64).reshape(-1))
+        assert sd.shape[0] == M
+        val = np.zeros(M)
+        terms = np.zeros((S, M), order="F") if "terms" in want else None
+        opt = lambda a: _d(a) if a is not None and a.size else None
+        rc = self.lib.fn("lognei_values")(self._h, S, opt(fp), float(xi), cm_ptr, ldm, opt(sd), M, opt(val), opt(terms))
+        if check:
+            self._chk(rc, "lognei_values")
+        return rc, val, terms
+
+    def lognei_batch(self, Xc, Xb, Z, out=0, jitter=0.0, xi=0.0, mean_b=None, mean_add=None,
+                     want=("lognei", "fplus", "mu", "var", "cvar", "cmean"), check=True):
+        """The log noisy expected improvement of every row of Xc under the handle's output `out`: baseline points Xb (B, D), standard
+        normals Z (B, S) of the caller's, jitter added to the baseline's covariance (no hidden default).  mean_b (B), mean_add (M):
+        the mean functor's values, or None.  Returns (status, lognei (M), fplus (S), mu (M), var (M), cvar (M), cmean (S, M)), None
+        for what `want` leaves out; status > 0: the 1-based first non-positive pivot of the baseline's covariance, nothing written."""
+        Xc = _c(Xc).reshape(-1, self.D)
+        Xb = _c(Xb).reshape(-1, self.D)
+        M, B = Xc.shape[0], Xb.shape[0]
+        Zn = np.asarray(Z, dtype=np.float64)
+        Zn = _c(Zn.reshape(B, -1), "F")
+        S = Zn.shape[1]
+        mb = _c(np.asarray(mean_b, dtype=np.float64).reshape(B)) if mean_b is not None else None
+        ma = _c(np.asarray(mean_add, dtype=np.float64).reshape(M)) if mean_add is not None else None
+        names = ("lognei", "fplus", "mu", "var", "cvar", "cmean")
+        res = {"lognei": np.zeros(M), "fplus": np.zeros(S), "mu": np.zeros(M), "var": np.zeros(M), "cvar": np.zeros(M),
+               "cmean": np.zeros((S, M), order="F")}
+        ptr = [_d(res[k]) if k in want else None for k in names]
+        rc = self.lib.fn("lognei_batch")(self._h, int(out), _d(Xb), B, _d(mb) if mb is not None else None, float(jitter), _d(Zn), S,
+                                         float(xi), _d(Xc), M, _d(ma) if ma is not None else None, *ptr, max(S, 1))
+        if check:
+            self._chk(rc, "lognei_batch")
+        return (rc,) + tuple(res[k] if k in want else None for k in names)
+
+    def nei_phase_ms(self):
+        """{baseline, factor_draws, solves, conditioning, kernel} of the last lognei_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(5)
+        self._chk(self.lib.fn("nei_phase_ms")(self._h, _d(ms)), "nei_phase_ms")
+        return dict(zip(("baseline", "factor_draws", "solves", "conditioning", "kernel"), ms.tolist()))
 
     # -- the posterior with its gradient in the query point (include/gpe_query_grad.h; HIP library only)
     def query_batch_grad(self, Xq, want=("kta", "var", "dkta", "dvar")):

@@ -20,7 +20,7 @@
 // No LDS, no atomics, nothing chosen from M: a candidate's numbers are bitwise the same in any batch.
 #include <cfloat>
 
-#include "dev.h"
+#include "logh.h" // cei_inv_T and cei_log_h (shared with nei.hip)
 
 namespace {
 constexpr int CEI_T = 64;          // threads per workgroup
@@ -29,38 +29,8 @@ constexpr int CEI_DEPTH = 60;      // partial quotients of T(x)
 constexpr double CEI_LOG_SQRT2PI = 0.91893853320467274178;
 constexpr double CEI_INV_SQRT2PI = 0.39894228040143267794;
 constexpr double CEI_INV_SQRT2 = 0.70710678118654752440;
+static_assert(CEI_XC == LOGH_XC && CEI_DEPTH == LOGH_DEPTH, "log Phi below and log h in logh.h change form at the same point");
 } // namespace
-
-// 1 / T(x) = x + 2 / (x + 3 / (x + ... + CEI_DEPTH / x)) for x > 0, bottom-up; x = inf: inf
-static __device__ __forceinline__ double cei_inv_T(double x)
-{
-    double t = x;
-#pragma unroll 4
-    for (int k = CEI_DEPTH; k >= 2; --k)
-        t = x + (double)k / t;
-    return t;
-}
-
-// log h(z) with Phi(z) / h(z) and phi(z) / h(z).  z = -inf: (-inf, inf, inf); z = +inf: (inf, 0, 0); NaN: NaN.
-static __device__ __forceinline__ void cei_log_h(double z, double& lh, double& r_Phi, double& r_phi)
-{
-    if (z < -CEI_XC) {
-        const double x = -z, t = cei_inv_T(x), rinv = x + 1.0 / t; // rinv = 1 / R(x)
-        lh = -0.5 * x * x - CEI_LOG_SQRT2PI - (log(rinv) + log(t));
-        r_Phi = t;
-        r_phi = rinv * t;
-        return;
-    }
-    const double a = fabs(z);
-    const double phi = exp(-0.5 * a * a) * CEI_INV_SQRT2PI;
-    const double Q = 0.5 * erfc(a * CEI_INV_SQRT2);
-    const double fm = Q == 0.0 ? phi : phi - a * Q; // h(-|z|); (inf 0 at |z| = inf)
-    const double h = z < 0.0 ? fm : z + fm;
-    const double Phi = z < 0.0 ? Q : 1.0 - Q;
-    lh = log(h);
-    r_Phi = Phi / h;
-    r_phi = phi / h;
-}
 
 // log Phi(u) with lambda(u) = phi(u) / Phi(u).  u = -inf: (-inf, inf); u = +inf: (0, 0); NaN: NaN.
 static __device__ __forceinline__ void cei_log_Phi(double u, double& lP, double& lam)

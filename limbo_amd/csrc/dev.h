@@ -601,6 +601,29 @@ struct MesArgs {
 };
 void launch_mes(hipStream_t s, const MesArgs& q);
 
+// ---- noisy expected improvement in the log domain (nei.hip; include/gpe_nei.h) -------------------------------------------
+// lognei[m] and, terms != null, the S terms (terms[s + m ldt]) of candidate m < M; one wave each.  fplus: the S incumbents, on the
+// device; cmean[s + m ldm]: the mean at candidate m given draw s.  cvar == null: the standard deviation csd[m]; otherwise
+// sqrt(cvar[m] > DBL_EPSILON ? cvar[m] : 0).  S <= GPE_NEI_MAX_SAMPLES.
+struct NeiArgs {
+    int S;
+    const double* fplus;
+    double xi;
+    const double* cmean;
+    int64_t ldm;
+    const double *csd, *cvar;
+    int64_t M;
+    double *lognei, *terms;
+    int64_t ldt;
+};
+void launch_lognei(hipStream_t s, const NeiArgs& q);
+// fplus[s] = max_i F[i + B s], s < S
+void launch_nei_colmax(hipStream_t s, const double* F, int64_t B, int S, double* fplus);
+// per candidate m < M, from column m of U (B x M, ldu): cvar[m] = var[m] - |U[:, m]|^2, mu_out[m] = kta[m] (+ add[m]; add == null:
+// nothing is added), cmean[s + m ldm] = mu_out[m] for s < S
+void launch_nei_cond(hipStream_t s, const double* U, int64_t ldu, int64_t B, const double* kta, const double* add, const double* var, int64_t M,
+                     int S, double* mu_out, double* cvar, double* cmean, int64_t ldm);
+
 // ---- posterior draws as functions of the query point (pathwise.hip; include/gpe_pathwise.h) -----------------------------
 // slots per (segment, column) of a pass's partial sums: the value and, grad, one per row of a point
 int paths_slots(bool grad, int R);

@@ -27,6 +27,7 @@
 #include "../../include/gpe_ehvi.h"
 #include "../../include/gpe_cei.h"
 #include "../../include/gpe_mes.h"
+#include "../../include/gpe_nei.h"
 #include "dev.h"
 #include "devbuf.h"
 #include "carve.h" // (the typed scratch carver of query.hpp: a template, so outside the extern "C" block below)
@@ -249,6 +250,7 @@ struct gpe_ctx {
     double ehvi_ms[3] = {0, 0, 0}; // the last gpe_ehvi2_batch call's solves, strip kernel and read-back, ms, while profiling is on
     double cei_ms[3] = {0, 0, 0}; // the last gpe_logcei_batch call's solves, kernel and read-back, ms, while profiling is on
     double mes_ms[3] = {0, 0, 0}; // the last gpe_mes_batch call's solves, kernel and read-back, ms, while profiling is on
+    double nei_ms[5] = {0, 0, 0, 0, 0}; // the last gpe_lognei_batch call's baseline pass with Sigma_b, factorisation with the draws, candidates' solves with the cross-covariance, conditioning, kernel with the read-back, ms, while profiling is on
     double select_ms[3] = {0, 0, 0}; // the last gpe_select_batch call's setup (Zt, kta, var_0), rounds and read-back, ms, while profiling is on
     double qgrad_ms[3] = {0, 0, 0}; // the last gpe_query_batch_grad call's forward part, backward solve and gradient kernel, ms, while profiling is on
     gpe_ctx* joint = nullptr; // the private scratch context that factors the joint posterior's covariance (joint.hpp): owned, never cloned
@@ -1311,6 +1313,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 #include "ehvi.hpp"   // the two-objective expected hypervolume improvement over a Pareto front (include/gpe_ehvi.h)
 #include "cei.hpp"    // constrained expected improvement in the log domain (include/gpe_cei.h)
 #include "mes.hpp"    // max-value entropy search in the log domain (include/gpe_mes.h)
+#include "nei.hpp"    // noisy expected improvement in the log domain (include/gpe_nei.h)
 #include "append.hpp" // a batch of samples appended in one blocked update (include/gpe_append.h)
 #include "remove.hpp" // samples removed by a blocked update of the factor (include/gpe_remove.h)
 #include "sparse.hpp" // the sparse pseudo-input GP: chunked V, ep, the weighted Gram, Lm, bet, predictions (include/gpe_sparse.h)

@@ -450,7 +450,8 @@ void potrf_blocked(gpe_ctx* c, double* A, int64_t N, int64_t M, const TailPlan& 
 // Z <- L^-1 B in place, B is N x M (ldb).  identity_structure: B starts as the identity, so at
 // step j only columns < j + jb are non-zero (L^-1 is lower triangular) — gp.hpp:260 restricted
 // to the triangle.  The 64-row diagonal solves are products with the stored block inverses.
-void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int64_t N, int64_t M, bool ident, int ph)
+// tile (0: by the size of each product): the tile of the updates, for a caller whose answer must not depend on M (nei.hpp).
+void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int64_t N, int64_t M, bool ident, int ph, int tile = 0)
 {
     hipStream_t s = c->stream;
     const int64_t ld = c->ld;
@@ -493,6 +494,7 @@ void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int6
                 g.m = oe - r0;
                 g.n = ncol;
                 g.k = jb;
+                g.tile = tile;
                 PhaseScope ps(c, ph, gemm_flops(g));
                 launch_gemm_sub(s, g);
             }
@@ -509,6 +511,7 @@ void trsm_left_blocked(gpe_ctx* c, const double* L, double* B, int64_t ldb, int6
             g.m = N - oe;
             g.n = ident ? oe : M;
             g.k = ow;
+            g.tile = tile;
             PhaseScope ps(c, ph, gemm_flops(g));
             launch_gemm_sub(s, g);
         }
