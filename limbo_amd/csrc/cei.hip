@@ -4,12 +4,12 @@
 //                                                                     u_k = (mu_k - t_k) / s_k
 //
 // h is the difference of two nearly equal numbers for z < 0 and underflows to 0 below z = -38.6 (acqui::EI, kg.hip's kg_f and
-// ehvi.hip's ehvi_ev form it as written and say so).  Here, for z < -CEI_XC, with x = -z and Mills' ratio R(x) = Phi(-x) / phi(x),
+// ehvi.hip's ehvi_ev form it as written and say so).  Here, for z < -LOGH_XC, with x = -z and Mills' ratio R(x) = Phi(-x) / phi(x),
 //   h(z) = Phi(z) T(x),  T(x) = 1 / R(x) - x = 1 / (x + 2 / (x + 3 / (x + ...))),   1 / R(x) = x + T(x)
 // every partial quotient positive, nothing subtracted:
 //   log Phi(-x) = -x^2 / 2 - log sqrt(2 pi) - log(x + T)        lambda(-x) = phi / Phi = x + T
 //   log h(-x)   = log Phi(-x) - log(1 / T)                      Phi / h = 1 / T,  phi / h = (x + T) / T
-// The fraction is evaluated bottom-up from quotient CEI_DEPTH whatever x is: at x = CEI_XC that leaves 2.4e-17 of T, less
+// The fraction is evaluated bottom-up from quotient LOGH_DEPTH whatever x is: at x = LOGH_XC that leaves 2.4e-17 of T, less
 // at every larger x, and at x = 1e100 every step is x + k / x = x.  Above the crossover the direct forms: phi - |z| Q(|z|) cancels
 // at most 1 / (1 - 3 R(3)) = 11.6 times there, and for z >= 0 it is added to z.
 //
@@ -18,32 +18,25 @@
 // wave's loads are contiguous.  The loop over the constraints has the wave-uniform bound C; thresholds and columns come from the
 // kernel's arguments.  The two region branches per belief diverge within a wave of mixed candidates; each side is then run once.
 // No LDS, no atomics, nothing chosen from M: a candidate's numbers are bitwise the same in any batch.
-#include <cfloat>
-
-#include "logh.h" // cei_inv_T and cei_log_h (shared with nei.hip)
+#include "belief.h"
+#include "logh.h" // the constants, logh_inv_T and cei_log_h
 
 namespace {
-constexpr int CEI_T = 64;          // threads per workgroup
-constexpr double CEI_XC = 3.0;     // the crossover: continued fraction for z < -CEI_XC
-constexpr int CEI_DEPTH = 60;      // partial quotients of T(x)
-constexpr double CEI_LOG_SQRT2PI = 0.91893853320467274178;
-constexpr double CEI_INV_SQRT2PI = 0.39894228040143267794;
-constexpr double CEI_INV_SQRT2 = 0.70710678118654752440;
-static_assert(CEI_XC == LOGH_XC && CEI_DEPTH == LOGH_DEPTH, "log Phi below and log h in logh.h change form at the same point");
+constexpr int CEI_T = 64; // threads per workgroup
 } // namespace
 
 // log Phi(u) with lambda(u) = phi(u) / Phi(u).  u = -inf: (-inf, inf); u = +inf: (0, 0); NaN: NaN.
 static __device__ __forceinline__ void cei_log_Phi(double u, double& lP, double& lam)
 {
-    if (u < -CEI_XC) {
-        const double x = -u, rinv = x + 1.0 / cei_inv_T(x);
-        lP = -0.5 * x * x - CEI_LOG_SQRT2PI - log(rinv);
+    if (u < -LOGH_XC) {
+        const double x = -u, rinv = x + 1.0 / logh_inv_T(x);
+        lP = -0.5 * x * x - LOGH_LOG_SQRT2PI - log(rinv);
         lam = rinv;
         return;
     }
     const double a = fabs(u);
-    const double phi = exp(-0.5 * a * a) * CEI_INV_SQRT2PI;
-    const double Q = 0.5 * erfc(a * CEI_INV_SQRT2);
+    const double phi = exp(-0.5 * a * a) * LOGH_INV_SQRT2PI;
+    const double Q = 0.5 * erfc(a * LOGH_INV_SQRT2);
     if (u < 0.0) {
         lP = log(Q);
         lam = phi / Q;
@@ -61,23 +54,17 @@ __global__ __launch_bounds__(CEI_T) void k_logcei(CeiArgs q)
         return;
     const double ninf = __longlong_as_double(0xfff0000000000000LL);
     const int C = q.C;
-    double sig = 0.0;
-    if (q.var) { // one model, several outputs: the shared sigma, clamped as gp.hpp:621-623
-        const double v = q.var[m];
-        sig = sqrt((v > DBL_EPSILON ? v : (v != v ? v : 0.0)) + q.var_add);
-    }
+    const double sig = belief_shared_sigma(q.b, m); // (one model, several outputs)
     double total = 0.0;
     bool any_nan = false, any_ninf = false;
 
-    if (q.with_ei || q.mu_out) {
-        double mu0 = q.mu[m + (int64_t)q.col[0] * q.ldmu];
-        if (q.add)
-            mu0 += q.add[m];
-        if (q.mu_out)
-            q.mu_out[m] = mu0;
+    if (q.with_ei || q.b.mu_out) {
+        const double mu0 = belief_mean(q.b, m, 0);
+        if (q.b.mu_out)
+            q.b.mu_out[m] = mu0;
         double t0 = 0.0, pm = 0.0, ps = 0.0;
         if (q.with_ei) {
-            const double s = q.var ? sig : q.sd[m];
+            const double s = belief_sd(q.b, m, 0, sig);
             const double d = mu0 - q.f_best - q.xi;
             if (s == 0.0) { // no uncertainty: the improvement itself, or none
                 t0 = d > 0.0 ? log(d) : (d != d ? d : ninf);
@@ -110,12 +97,10 @@ __global__ __launch_bounds__(CEI_T) void k_logcei(CeiArgs q)
     }
 
     for (int k = 0; k < C; ++k) {
-        double mu = q.mu[m + (int64_t)q.col[1 + k] * q.ldmu];
-        if (q.add)
-            mu += q.add[m + (int64_t)(1 + k) * q.lda];
-        if (q.mu_out)
-            q.mu_out[m + (int64_t)(1 + k) * q.ldm] = mu;
-        const double s = q.var ? sig : q.sd[m + (int64_t)(1 + k) * q.lds];
+        const double mu = belief_mean(q.b, m, 1 + k);
+        if (q.b.mu_out)
+            q.b.mu_out[m + (int64_t)(1 + k) * q.b.ldm] = mu;
+        const double s = belief_sd(q.b, m, 1 + k, sig);
         const double d = mu - q.thr[k];
         double term, pm, ps;
         if (s == 0.0) { // no uncertainty: met or not

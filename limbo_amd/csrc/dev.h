@@ -544,67 +544,66 @@ void launch_sel_round(hipStream_t s, const SelRound& g, int t); // round t: gath
 void launch_kg_envelope(hipStream_t s, const double* a, int A, const double* B, int64_t ldb, int64_t M, const double* var, double obs_noise,
                         int with_self, const double* mu_c, double* kg, int* nseg);
 
+// ---- the marginal beliefs of an acquisition's candidates (belief.h; ehvi.hip, cei.hip, mes.hip) ---------------------------
+// Belief j of candidate m: the mean mu[m + col[j] ldmu] (+ add[m + j lda]; add == null: nothing is added); var == null: the standard
+// deviation sd[m + j lds]; otherwise one model's outputs share sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  mu_out (may be
+// null): the means as used, column j at mu_out + j ldm.
+constexpr int BELIEF_MAX = 17; // GPE_CEI_MAX_CONSTRAINTS + 1 (acq.hpp holds it to that)
+struct BeliefArgs {
+    const double *mu, *add, *sd, *var;
+    int64_t ldmu, lda, lds;
+    double var_add;
+    int col[BELIEF_MAX];
+    double* mu_out;
+    int64_t ldm;
+};
+
 // ---- the two-objective expected hypervolume improvement (ehvi.hip; include/gpe_ehvi.h) ----------------------------------
 // ehvi[m] and, partials != null, the four partials (column c at partials + c ldp) of candidate m < M over the prepared front
-// (device, row-major n x 2, n <= GPE_EHVI_MAX_FRONT: it sits in LDS) and (r1, r2); one wave each.  The belief of candidate m:
-// means mu1[m] (+ add1[m]) and mu2[m] (+ add2[m]; add1 == null: nothing is added); var == null: the standard deviations s1[m], s2[m];
-// otherwise both are sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  mu_out (may be null): the two means as used, column k at
-// mu_out + k ldm.
+// (device, row-major n x 2, n <= GPE_EHVI_MAX_FRONT: it sits in LDS) and (r1, r2); one wave each.  Beliefs 0 and 1 of b: the objectives.
 struct EhviArgs {
     const double* front;
     int n;
     double r1, r2;
-    const double *mu1, *mu2, *add1, *add2, *s1, *s2, *var;
-    double var_add;
+    BeliefArgs b;
     int64_t M;
-    double *ehvi, *partials, *mu_out;
-    int64_t ldp, ldm;
+    double *ehvi, *partials;
+    int64_t ldp;
 };
 void launch_ehvi2(hipStream_t s, const EhviArgs& q);
 
 // ---- constrained expected improvement in the log domain (cei.hip; include/gpe_cei.h) ------------------------------------
 // logcei[m] and, where asked, terms (column j at terms + j ldt, j <= C) and partials (column j at partials + j ldp, j < 2 + 2 C) of
-// candidate m < M; one thread each.  Belief j (0: the objective, 1 .. C: the constraints) of candidate m: the mean mu[m + col[j] ldmu]
-// (+ add[m + j lda]; add == null: nothing is added); var == null: the standard deviation sd[m + j lds]; otherwise every one is
-// sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  with_ei == 0: belief 0 is not read.  mu_out (may be null): the 1 + C means
-// as used, column j at mu_out + j ldm.
+// candidate m < M; one thread each.  Belief 0 of b: the objective (with_ei == 0: not read), 1 .. C: the constraints.
 struct CeiArgs {
     int with_ei, C;
     double f_best, xi;
     double thr[16]; // GPE_CEI_MAX_CONSTRAINTS
-    int col[17];
-    const double *mu, *add, *sd, *var;
-    int64_t ldmu, lda, lds;
-    double var_add;
+    BeliefArgs b;
     int64_t M;
-    double *logcei, *terms, *partials, *mu_out;
-    int64_t ldt, ldp, ldm;
+    double *logcei, *terms, *partials;
+    int64_t ldt, ldp;
 };
 void launch_logcei(hipStream_t s, const CeiArgs& q);
 
 // ---- max-value entropy search in the log domain (mes.hip; include/gpe_mes.h) --------------------------------------------
 // logmes[m] and, where asked, terms (column j at terms + j ldt, j < J) and partials (d/d mu_j at partials + j ldp, d/d s_j at
-// partials + (J + j) ldp) of candidate m < M; one wave each.  ystar: K x J column-major on the device, finite.  Belief j of candidate
-// m: the mean mu[m + col[j] ldmu] (+ add[m + j lda]; add == null: nothing is added); var == null: the standard deviation
-// sd[m + j lds]; otherwise every one is sqrt((var[m] > DBL_EPSILON ? var[m] : 0) + var_add).  mu_out (may be null): the J means as
-// used, column j at mu_out + j ldm.
+// partials + (J + j) ldp) of candidate m < M; one wave each.  ystar: K x J column-major on the device, finite.  Beliefs 0 .. J - 1 of
+// b: the outputs (J <= GPE_MES_MAX_OUTPUTS).
 struct MesArgs {
     int J, K;
-    int col[8]; // GPE_MES_MAX_OUTPUTS
     const double* ystar;
-    const double *mu, *add, *sd, *var;
-    int64_t ldmu, lda, lds;
-    double var_add;
+    BeliefArgs b;
     int64_t M;
-    double *logmes, *terms, *partials, *mu_out;
-    int64_t ldt, ldp, ldm;
+    double *logmes, *terms, *partials;
+    int64_t ldt, ldp;
 };
 void launch_mes(hipStream_t s, const MesArgs& q);
 
 // ---- noisy expected improvement in the log domain (nei.hip; include/gpe_nei.h) -------------------------------------------
 // lognei[m] and, terms != null, the S terms (terms[s + m ldt]) of candidate m < M; one wave each.  fplus: the S incumbents, on the
 // device; cmean[s + m ldm]: the mean at candidate m given draw s.  cvar == null: the standard deviation csd[m]; otherwise
-// sqrt(cvar[m] > DBL_EPSILON ? cvar[m] : 0).  S <= GPE_NEI_MAX_SAMPLES.
+// sqrt(cvar[m] > DBL_EPSILON ? cvar[m] : 0) (belief.h's clamp).  S <= GPE_NEI_MAX_SAMPLES.
 struct NeiArgs {
     int S;
     const double* fplus;

@@ -16,7 +16,8 @@
 // no workgroup waits for another; no atomics.  Nothing here is chosen from M.
 #include <cfloat>
 
-#include "dev.h"
+#include "belief.h"
+#include "logh.h" // the normal constants
 
 namespace {
 constexpr int EHVI_W = 4;            // waves = candidates per workgroup
@@ -51,8 +52,8 @@ static __device__ __forceinline__ Ev ehvi_ev(double mu, double s, double t)
     const double a = -fabs(z);
     double fm = 0.0, Q = 0.0, phi = 0.0; // f(-|z|), Phi(-|z|), phi(z); all 0 at |z| = inf
     if (a >= -DBL_MAX) {
-        phi = exp(-0.5 * a * a) * 0.39894228040143267794; // 1 / sqrt(2 pi)
-        Q = 0.5 * erfc(-a * 0.70710678118654752440);
+        phi = exp(-0.5 * a * a) * LOGH_INV_SQRT2PI;
+        Q = 0.5 * erfc(-a * LOGH_INV_SQRT2);
         fm = fmax(phi + a * Q, 0.0);
     }
     e.phi = phi;
@@ -87,19 +88,9 @@ __global__ __launch_bounds__(EHVI_T) void k_ehvi2(EhviArgs q)
     if (m >= q.M) // (wave-uniform; no barrier follows)
         return;
 
-    double mu1 = q.mu1[m], mu2 = q.mu2[m], s1, s2;
-    if (q.add1) {
-        mu1 += q.add1[m];
-        mu2 += q.add2[m];
-    }
-    if (q.var) { // one model, two outputs: the shared sigma, clamped as gp.hpp:621-623
-        const double v = q.var[m];
-        s1 = s2 = sqrt((v > DBL_EPSILON ? v : (v != v ? v : 0.0)) + q.var_add);
-    }
-    else {
-        s1 = q.s1[m];
-        s2 = q.s2[m];
-    }
+    const double mu1 = belief_mean(q.b, m, 0), mu2 = belief_mean(q.b, m, 1);
+    const double sig = belief_shared_sigma(q.b, m); // (one model, two outputs)
+    const double s1 = belief_sd(q.b, m, 0, sig), s2 = belief_sd(q.b, m, 1, sig);
     const double r1 = q.r1, r2 = q.r2, inf = __longlong_as_double(0x7ff0000000000000LL);
 
     double av = 0.0, am1 = 0.0, as1 = 0.0, am2 = 0.0, as2 = 0.0;
@@ -167,9 +158,9 @@ __global__ __launch_bounds__(EHVI_T) void k_ehvi2(EhviArgs q)
         q.partials[m + 2 * q.ldp] = am2;
         q.partials[m + 3 * q.ldp] = as2;
     }
-    if (q.mu_out) {
-        q.mu_out[m] = mu1;
-        q.mu_out[m + q.ldm] = mu2;
+    if (q.b.mu_out) {
+        q.b.mu_out[m] = mu1;
+        q.b.mu_out[m + q.b.ldm] = mu2;
     }
 }
 

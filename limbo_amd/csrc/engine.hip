@@ -1309,6 +1309,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 #include "pathwise.hpp" // posterior draws as functions of the query point: Fourier features + Matheron's rule (include/gpe_pathwise.h)
 #include "joint.hpp" // the joint posterior over a point batch: covariance, draws, arg-max (include/gpe_joint.h)
 #include "select.hpp" // greedy batch selection with hallucinated observations (include/gpe_batch_select.h)
+#include "acq.hpp"    // what the acquisition functions below share: the chunk rule, a chunk's steps, the two pipelines
 #include "kg.hpp"     // the knowledge gradient over a finite alternative set (include/gpe_kg.h)
 #include "ehvi.hpp"   // the two-objective expected hypervolume improvement over a Pareto front (include/gpe_ehvi.h)
 #include "cei.hpp"    // constrained expected improvement in the log domain (include/gpe_cei.h)

@@ -300,14 +300,6 @@ int gpe_joint_max_points(gpe_handle c, int64_t* M_max)
     return GPE_OK;
 }
 
-int gpe_joint_phase_ms(gpe_handle c, double* ms4)
-{
-    if (!c || !ms4)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int q = 0; q < 4; ++q)
-        ms4[q] = c->joint_ms[q];
-    return GPE_OK;
-}
+int gpe_joint_phase_ms(gpe_handle c, double* ms4) { return phase_ms_get(c, &gpe_ctx::joint_ms, ms4); }
 
 int gpe_debug_cov_plan(int64_t M, int64_t N, int cus, int64_t* out, int64_t cap_rows) { return joint_cov_plan(M, N, cus, out, cap_rows); }

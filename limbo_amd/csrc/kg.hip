@@ -14,7 +14,7 @@
 // O(A^2) pair steps are one fp64 division each; hi / succ go to LDS and one lane walks them.  Fixed order throughout, no atomics.
 #include <cfloat>
 
-#include "dev.h"
+#include "logh.h" // the normal constants
 
 namespace {
 constexpr int KG_T = 256; // threads per workgroup
@@ -28,8 +28,8 @@ static __device__ __forceinline__ double kg_f(double z)
     const double t = -fabs(z);
     if (!(t >= -DBL_MAX)) // -inf or NaN
         return t != t ? t : 0.0;
-    const double phi = exp(-0.5 * t * t) * 0.39894228040143267794; // 1 / sqrt(2 pi)
-    const double Phi = 0.5 * erfc(-t * 0.70710678118654752440);
+    const double phi = exp(-0.5 * t * t) * LOGH_INV_SQRT2PI;
+    const double Phi = 0.5 * erfc(-t * LOGH_INV_SQRT2);
     return fmax(phi + t * Phi, 0.0);
 }
 

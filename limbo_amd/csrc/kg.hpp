@@ -1,10 +1,6 @@
 // kg.hpp — the knowledge gradient over a finite alternative set (include/gpe_kg.h): host side.  Kernel: kg.hip.
-// A part of engine.hip's translation unit (included there, once, behind query.hpp, joint.hpp and select.hpp, whose helpers it shares).
+// A part of engine.hip's translation unit (included there, once, behind acq.hpp, whose chunk rule and chunk steps it shares).
 #pragma once
-
-// Candidates per chunk of the N x M layout (fewer samples than one outer panel): the blocked solve picks its tile from the
-// column count above some ten thousand columns, and a candidate's answer must not depend on the batch around it
-static const int64_t kKgNmChunk = 8192;
 
 // Called with the handle's mutex held; A in [1, GPE_KG_MAX_ALTERNATIVES], M > 0, arguments checked.
 static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, const double* Xc, int64_t M, const double* mu_c,
@@ -16,8 +12,7 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
     const int D = c->D;
     PhaseDrain pd(c);
     // two sets of chunk buffers in one lease of the scratch: the alternatives' (resident for the call: Z_a, a) and a candidate chunk's
-    const int64_t ma_max = round_up(A, 64);
-    const int64_t mc_max = qt_serves(c) ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk);
+    const int64_t ma_max = round_up(A, 64), mc_max = cand_chunk_max(c, M);
     QtBufs ba = served_layout(c, ma_max, N), bc = served_layout(c, mc_max, N);
     const int64_t ldx = ma_max + 16; // the cross-covariance: A x mc, column-major, alternatives contiguous (even: 16-byte columns)
     double *dA = nullptr, *dC = nullptr, *dKg = nullptr, *dMu = nullptr;
@@ -49,25 +44,8 @@ static int kg_impl(gpe_ctx* c, const double* Xa, int64_t A, const double* mu_a, 
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
         const bool want_kta = with_self && !mu_c;
         const int u0 = mk.mark();
-        // the chunk's head, solve and variance as a query's
-        chunk_head(c, bc, Xc + m0 * D, true, mc, true, want_kta, nullptr, 0, mc);
-        const ZView zc = chunk_solve(c, bc, mc);
-        chunk_var(c, bc, mc, zc);
-        {
-            // c = k(Xa, Xc) - Z_a^T Z_c on the matrix cores: the tile from N alone, the k range whole (no split: nothing of
-            // the product depends on M or on where in the batch a candidate stands)
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * (double)A * mc * N);
-            launch_build_Ks(s, ba.dQt, ba.ldq, A, bc.dQt, bc.ldq, mc, c->kp, dC, ldx);
-            GemmArgs g{};
-            g.C = dC;
-            g.ldc = ldx;
-            z_operands(g, za, zc);
-            g.m = A;
-            g.n = mc;
-            g.k = N;
-            g.tile = qt_tile(N);
-            launch_gemm_sub(s, g);
-        }
+        const ZView zc = cand_chunk(c, bc, Xc + m0 * D, mc, want_kta);
+        cross_cov(c, ba, za, A, bc, zc, mc, dC, ldx);
         if (with_self && mu_c)
             HIPCHK(c, hipMemcpyAsync(dMu, mu_c + m0, sizeof(double) * (size_t)mc, hipMemcpyHostToDevice, s));
         const int u1 = mk.mark();
@@ -125,7 +103,7 @@ int gpe_kg_envelope(gpe_handle c, const double* a, int64_t A, const double* B, i
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t s = c->stream;
-    const int64_t mc_max = std::min<int64_t>(M, 16384); // columns on the device at once
+    const int64_t mc_max = std::min<int64_t>(M, kValuesChunk); // columns on the device at once
     double *dA = nullptr, *dB = nullptr, *dKg = nullptr;
     int* dSeg = nullptr;
     QueryScratch qs(c);
@@ -150,12 +128,4 @@ int gpe_kg_envelope(gpe_handle c, const double* a, int64_t A, const double* B, i
     return GPE_OK;
 }
 
-int gpe_kg_phase_ms(gpe_handle c, double* ms4)
-{
-    if (!c || !ms4)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int q = 0; q < 4; ++q)
-        ms4[q] = c->kg_ms[q];
-    return GPE_OK;
-}
+int gpe_kg_phase_ms(gpe_handle c, double* ms4) { return phase_ms_get(c, &gpe_ctx::kg_ms, ms4); }

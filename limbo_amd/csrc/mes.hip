@@ -4,13 +4,13 @@
 //   logmes[m]   = log sum_j exp(terms[m, j])
 //
 // t as written is 0 / 0 below g = -38.5 and exactly 0, hence flat, above g = +38.6.  Here log t and r = t' / t come from three forms,
-// with x = |g|, Mills' ratio R(x) = Phi(-x) / phi(x), 1 / T = x + c2, c2 = 2 / (x + 3 / (x + ...)) (cei.hip's fraction; the inner tail
+// with x = |g|, Mills' ratio R(x) = Phi(-x) / phi(x), 1 / T = x + c2, c2 = 2 / (x + 3 / (x + ...)) (logh.h's fraction; the inner tail
 // IS c2, so 1 - x T = c2 T is never formed by subtraction) and lambda = phi / Phi:
-//   g < -MES_XC   lambda = x + T     t = log sqrt(2 pi) + log(x + T) - x T / 2     (>= 2 minus <= 1 / 2)      t' = -(lambda / 2) c2 T
-//   g > +MES_XC   Q = phi R          log t = -g^2 / 2 - log sqrt(2 pi) + log B,  B = g / (2 (1 - Q)) + R (-log1p(-Q) / Q)   (all > 0)
+//   g < -LOGH_XC   lambda = x + T     t = log sqrt(2 pi) + log(x + T) - x T / 2     (>= 2 minus <= 1 / 2)      t' = -(lambda / 2) c2 T
+//   g > +LOGH_XC   Q = phi R          log t = -g^2 / 2 - log sqrt(2 pi) + log B,  B = g / (2 (1 - Q)) + R (-log1p(-Q) / Q)   (all > 0)
 //                                    t' / t = -[1 + g (g + phi / (1 - Q))] / (2 (1 - Q) B)                      (no phi left: -> -g)
 //   otherwise     t = g lambda / 2 - log Phi,   t' = -(lambda / 2) (1 + g (g + lambda))
-// The fraction is evaluated bottom-up from quotient MES_DEPTH whatever x is: at x = MES_XC that leaves 2.4e-17 of T,
+// The fraction is evaluated bottom-up from quotient LOGH_DEPTH whatever x is: at x = LOGH_XC that leaves 2.4e-17 of T,
 // less at every larger x, and at x = 1e100 every step is x + k / x = x.
 //
 // One WAVE per candidate, MES_W waves per workgroup.  For each output j in turn the workgroup stages ystar's column j in LDS, shared
@@ -20,29 +20,13 @@
 // __shfl_xor trees, per lane they run over k ascending: an order fixed by K alone.  Lane j keeps output j's term and partials; the
 // log-sum-exp over j is a tree over lanes 0 .. 7.  The region branches diverge within a wave; each side is then run once.  No atomics,
 // nothing chosen from M: a candidate's numbers are bitwise the same in any batch.
-#include <cfloat>
-
-#include "dev.h"
+#include "belief.h"
+#include "logh.h" // the constants and logh_c2
 
 namespace {
 constexpr int MES_W = 2;           // waves (candidates) per workgroup
 constexpr int MES_T = 64 * MES_W;  // threads per workgroup
-constexpr double MES_XC = 3.0;     // the crossover: continued fraction for |g| > MES_XC
-constexpr int MES_DEPTH = 60;      // partial quotients of T(x)
-constexpr double MES_LOG_SQRT2PI = 0.91893853320467274178;
-constexpr double MES_INV_SQRT2PI = 0.39894228040143267794;
-constexpr double MES_INV_SQRT2 = 0.70710678118654752440;
 } // namespace
-
-// c2(x) = 2 / (x + 3 / (x + ... + MES_DEPTH / x)) for x > 0, bottom-up (cei.hip's cei_inv_T is x + c2); x = inf: 0
-static __device__ __forceinline__ double mes_c2(double x)
-{
-    double t = x;
-#pragma unroll 4
-    for (int k = MES_DEPTH; k >= 3; --k)
-        t = x + (double)k / t;
-    return 2.0 / t;
-}
 
 // log t(g) and r = t'(g) / t(g) <= 0.  g = -inf: (+inf, 0); g = +inf: (-inf, 0); NaN: NaN.
 static __device__ __forceinline__ void mes_log_t(double g, double& lt, double& r)
@@ -54,27 +38,27 @@ static __device__ __forceinline__ void mes_log_t(double g, double& lt, double& r
         r = 0.0;
         return;
     }
-    if (x > MES_XC) {
-        const double c2 = mes_c2(x), T = 1.0 / (x + c2);
+    if (x > LOGH_XC) {
+        const double c2 = logh_c2(x), T = 1.0 / (x + c2);
         if (g < 0.0) {
             const double lam = x + T;
-            const double t = MES_LOG_SQRT2PI + log(lam) - 0.5 * x * T;
+            const double t = LOGH_LOG_SQRT2PI + log(lam) - 0.5 * x * T;
             lt = log(t);
             r = -(0.5 * lam) * c2 * T / t;
         }
         else {
-            const double phi = exp(-0.5 * x * x) * MES_INV_SQRT2PI;
+            const double phi = exp(-0.5 * x * x) * LOGH_INV_SQRT2PI;
             const double R = 1.0 / (x + T);
             const double Q = phi * R, P = 1.0 - Q;
             const double quot = Q > 0.0 ? -log1p(-Q) / Q : 1.0;
             const double B = x / (2.0 * P) + R * quot;
-            lt = -0.5 * x * x - MES_LOG_SQRT2PI + log(B);
+            lt = -0.5 * x * x - LOGH_LOG_SQRT2PI + log(B);
             r = -(1.0 + x * (x + phi / P)) / (2.0 * P * B);
         }
         return;
     }
-    const double phi = exp(-0.5 * x * x) * MES_INV_SQRT2PI;
-    const double Q = 0.5 * erfc(x * MES_INV_SQRT2);
+    const double phi = exp(-0.5 * x * x) * LOGH_INV_SQRT2PI;
+    const double Q = 0.5 * erfc(x * LOGH_INV_SQRT2);
     const double Phi = g < 0.0 ? Q : 1.0 - Q;
     const double lP = g < 0.0 ? log(Q) : log1p(-Q);
     const double lam = phi / Phi;
@@ -96,11 +80,7 @@ __global__ __launch_bounds__(MES_T) void k_mes(MesArgs q)
     const double inf = __longlong_as_double(0x7ff0000000000000LL), nan = __longlong_as_double(0x7ff8000000000000LL);
     const double logK = log((double)K);
 
-    double sig = 0.0;
-    if (live && q.var) { // one model, several outputs: the shared sigma, clamped as gp.hpp:621-623
-        const double v = q.var[m];
-        sig = sqrt((v > DBL_EPSILON ? v : (v != v ? v : 0.0)) + q.var_add);
-    }
+    const double sig = live ? belief_shared_sigma(q.b, m) : 0.0; // (one model, several outputs)
     double term = -inf, pm = 0.0, ps = 0.0; // lane j < J: output j's
 
     for (int j = 0; j < J; ++j) {
@@ -110,12 +90,10 @@ __global__ __launch_bounds__(MES_T) void k_mes(MesArgs q)
         __syncthreads();
         if (!live)
             continue;
-        double mu = q.mu[m + (int64_t)q.col[j] * q.ldmu];
-        if (q.add)
-            mu += q.add[m + (int64_t)j * q.lda];
-        if (q.mu_out && lane == 0)
-            q.mu_out[m + (int64_t)j * q.ldm] = mu;
-        const double s = q.var ? sig : q.sd[m + (int64_t)j * q.lds];
+        const double mu = belief_mean(q.b, m, j);
+        if (q.b.mu_out && lane == 0)
+            q.b.mu_out[m + (int64_t)j * q.b.ldm] = mu;
+        const double s = belief_sd(q.b, m, j, sig);
         double tj, mj = 0.0, sj = 0.0;
         if (mu != mu || s != s)
             tj = mj = sj = nan;

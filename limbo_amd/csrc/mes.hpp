@@ -1,5 +1,5 @@
 // mes.hpp — max-value entropy search in the log domain (include/gpe_mes.h): host side.  Kernel: mes.hip.
-// A part of engine.hip's translation unit (included there, once, behind cei.hpp, whose chunking it follows).
+// A part of engine.hip's translation unit (included there, once, behind acq.hpp, whose two pipelines run it).
 #pragma once
 
 // what both entry points check before anything needs the device
@@ -11,6 +11,22 @@ static bool mes_args_ok(int J, int K, const double* ystar)
         if (!std::isfinite(ystar[i]))
             return false;
     return true;
+}
+
+// the kernel for one chunk of either pipeline (acq.hpp); the constant input: ystar; outputs: logmes, terms, partials
+static void mes_launch(const AcqChunk& ch, int J, int K, bool want_terms, bool want_partials)
+{
+    MesArgs q{};
+    q.J = J;
+    q.K = K;
+    q.ystar = ch.konst;
+    q.b = ch.b;
+    q.M = ch.mc;
+    q.logmes = ch.dev[0];
+    q.terms = want_terms ? ch.dev[1] : nullptr;
+    q.partials = want_partials ? ch.dev[2] : nullptr;
+    q.ldt = q.ldp = ch.ld;
+    launch_mes(ch.s, q);
 }
 
 // The kernel alone, on host-supplied beliefs: any handle, computed or not (its device, stream and scratch are all it takes)
@@ -28,135 +44,9 @@ int gpe_mes_values(gpe_handle c, int J, int K, const double* ystar, const double
             return GPE_ERR_ARG;
     if (c->host_K)
         return GPE_ERR_UNSUPPORTED;
-    DevGuard g(c);
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipStream_t s = c->stream;
-    const int64_t mc_max = std::min<int64_t>(M, 16384); // candidates on the device at once
-    double *dY = nullptr, *dMu = nullptr, *dSd = nullptr, *dV = nullptr, *dT = nullptr, *dP = nullptr;
-    QueryScratch qs(c);
-    if (const int e = qs.carve([&](Carver& cv) {
-            dY = cv.take<double>((size_t)(J * K));
-            dMu = cv.take<double>((size_t)(J * mc_max));
-            dSd = cv.take<double>((size_t)(J * mc_max));
-            dV = cv.take<double>((size_t)mc_max);
-            dT = cv.take<double>((size_t)(J * mc_max));
-            dP = cv.take<double>((size_t)(2 * J * mc_max));
-        }))
-        return e;
-    HIPCHK(c, hipMemcpyAsync(dY, ystar, sizeof(double) * (size_t)(J * K), hipMemcpyHostToDevice, s));
-    for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
-        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        HIPCHK(c, copy2d_from_host(dMu, mc_max, mu + m0, M, mc, J, s));
-        HIPCHK(c, copy2d_from_host(dSd, mc_max, sd + m0, M, mc, J, s));
-        MesArgs q{};
-        q.J = J;
-        q.K = K;
-        for (int j = 0; j < J; ++j)
-            q.col[j] = j;
-        q.ystar = dY;
-        q.mu = dMu;
-        q.sd = dSd;
-        q.ldmu = q.lds = mc_max;
-        q.M = mc;
-        q.logmes = dV;
-        q.terms = terms ? dT : nullptr;
-        q.partials = partials ? dP : nullptr;
-        q.ldt = q.ldp = mc_max;
-        launch_mes(s, q);
-        HIPCHK(c, hipMemcpyAsync(logmes + m0, dV, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
-        if (terms)
-            HIPCHK(c, copy2d_to_host(terms + m0, M, dT, mc_max, mc, J, s));
-        if (partials)
-            HIPCHK(c, copy2d_to_host(partials + m0, M, dP, mc_max, mc, 2 * J, s));
-        if (const int e = stream_wait(c, "mes_values", true))
-            return e;
-    }
-    return GPE_OK;
-}
-
-// Called with the handle's mutex held; M > 0, arguments checked.
-static int mes_impl(gpe_ctx* c, int J, const int* outs, int K, const double* ystar, const double* Xc, int64_t M, const double* mean_add,
-                    double var_add, double* logmes, double* terms, double* partials, double* mu, double* var)
-{
-    hipStream_t s = c->stream;
-    digest_kernel(c);
-    const int64_t N = c->N;
-    const int D = c->D;
-    PhaseDrain pd(c);
-    // the chunk of a query, as cei_impl's candidates (a candidate's answer must not depend on the batch around it)
-    const int64_t mc_max = qt_serves(c) ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk);
-    QtBufs bc = served_layout(c, mc_max, N);
-    double *dY = nullptr, *dAdd = nullptr, *dV = nullptr, *dT = nullptr, *dP = nullptr, *dMu = nullptr;
-    QueryScratch qs(c);
-    if (const int e = qs.carve([&](Carver& cv) {
-            qt_carve(bc, cv);
-            dY = cv.take<double>((size_t)(J * K));
-            dAdd = cv.take<double>((size_t)(J * mc_max));
-            dV = cv.take<double>((size_t)mc_max);
-            dT = cv.take<double>((size_t)(J * mc_max));
-            dP = cv.take<double>((size_t)(2 * J * mc_max));
-            dMu = cv.take<double>((size_t)(J * mc_max));
-        }))
-        return e;
-    HIPCHK(c, hipMemcpyAsync(dY, ystar, sizeof(double) * (size_t)(J * K), hipMemcpyHostToDevice, s));
-
-    Marks mk(c->pool, s, c->prof);
-    double ms[3] = {0, 0, 0};
-    chunk_begin(c, bc, true);
-    int rc = GPE_OK;
-    for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
-        const int64_t mc = std::min<int64_t>(mc_max, M - m0);
-        const int u0 = mk.mark();
-        // the chunk's head (with k^T alpha of every output), solve and variance as a query's
-        chunk_head(c, bc, Xc + m0 * D, true, mc, true, true, nullptr, 0, mc);
-        const ZView zc = chunk_solve(c, bc, mc);
-        chunk_var(c, bc, mc, zc);
-        if (mean_add)
-            HIPCHK(c, copy2d_from_host(dAdd, mc_max, mean_add + m0, M, mc, J, s));
-        const int u1 = mk.mark();
-        {
-            PhaseScope ps(c, GPE_PH_QUERY, 0.0);
-            MesArgs q{};
-            q.J = J;
-            q.K = K;
-            for (int j = 0; j < J; ++j)
-                q.col[j] = outs[j];
-            q.ystar = dY;
-            q.mu = bc.dKta;
-            q.ldmu = bc.mc_max;
-            q.add = mean_add ? dAdd : nullptr;
-            q.lda = mc_max;
-            q.var = bc.dVar;
-            q.var_add = var_add;
-            q.M = mc;
-            q.logmes = dV;
-            q.terms = terms ? dT : nullptr;
-            q.partials = partials ? dP : nullptr;
-            q.mu_out = mu ? dMu : nullptr;
-            q.ldt = q.ldp = q.ldm = mc_max;
-            launch_mes(s, q);
-        }
-        const int u2 = mk.mark();
-        if (logmes)
-            HIPCHK(c, hipMemcpyAsync(logmes + m0, dV, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
-        if (terms)
-            HIPCHK(c, copy2d_to_host(terms + m0, M, dT, mc_max, mc, J, s));
-        if (partials)
-            HIPCHK(c, copy2d_to_host(partials + m0, M, dP, mc_max, mc, 2 * J, s));
-        if (mu)
-            HIPCHK(c, copy2d_to_host(mu + m0, M, dMu, mc_max, mc, J, s));
-        if (var)
-            HIPCHK(c, hipMemcpyAsync(var + m0, bc.dVar, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
-        const int u3 = mk.mark();
-        rc = stream_wait(c, "mes_batch", true);
-        ms[0] += mk.ms(u0, u1);
-        ms[1] += mk.ms(u1, u2);
-        ms[2] += mk.ms(u2, u3);
-    }
-    if (c->prof && rc == GPE_OK)
-        for (int q = 0; q < 3; ++q)
-            c->mes_ms[q] = ms[q];
-    return rc;
+    // (beliefs, pieces and their count, constant input and its length, outputs and their count, the wait's name)
+    const AcqValues a{J, {{mu, sd, 0, J}}, 1, ystar, (int64_t)J * K, {{logmes, 1}, {terms, J}, {partials, 2 * J}}, 3, "mes_values"};
+    return acq_values(c, M, a, [=](const AcqChunk& ch) { mes_launch(ch, J, K, terms != nullptr, partials != nullptr); });
 }
 
 int gpe_mes_batch(gpe_handle c, int J, const int* outs, int K, const double* ystar, const double* Xc, int64_t M, const double* mean_add,
@@ -168,26 +58,15 @@ int gpe_mes_batch(gpe_handle c, int J, const int* outs, int K, const double* yst
         return GPE_ERR_STATE;
     if (c->host_K)
         return GPE_ERR_UNSUPPORTED;
-    for (int j = 0; j < J; ++j) {
-        if (outs[j] < 0 || outs[j] >= c->P)
-            return GPE_ERR_ARG;
-        for (int i = 0; i < j; ++i)
-            if (outs[i] == outs[j])
-                return GPE_ERR_ARG;
-    }
+    if (!outs_ok(c, outs, J))
+        return GPE_ERR_ARG;
     if (M == 0 || (!logmes && !terms && !partials && !mu && !var))
         return GPE_OK;
     DevGuard g(c);
     std::lock_guard<std::mutex> lk(c->mu);
-    return mes_impl(c, J, outs, K, ystar, Xc, M, mean_add, var_add, logmes, terms, partials, mu, var);
+    // (belief columns and their count, mean_add, var_add, constant input and its length, outputs and their count, mu, var, phases, the wait's name)
+    const AcqCall a{outs, J, mean_add, var_add, ystar, (int64_t)J * K, {{logmes, 1}, {terms, J}, {partials, 2 * J}}, 3, mu, var, c->mes_ms, "mes_batch"};
+    return acq_batch(c, Xc, M, a, [=](const AcqChunk& ch) { mes_launch(ch, J, K, terms != nullptr, partials != nullptr); });
 }
 
-int gpe_mes_phase_ms(gpe_handle c, double* ms3)
-{
-    if (!c || !ms3)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int q = 0; q < 3; ++q)
-        ms3[q] = c->mes_ms[q];
-    return GPE_OK;
-}
+int gpe_mes_phase_ms(gpe_handle c, double* ms3) { return phase_ms_get(c, &gpe_ctx::mes_ms, ms3); }

@@ -18,8 +18,7 @@
 // k_nei_colmax: fplus[s] = max_i F[i, s], one wave per draw.  k_nei_cond: per candidate, one wave: |u|^2 of its column of U = L_b^-1 c
 // (lanes over the baseline points ascending, a __shfl_xor tree), cvar = var - |u|^2, the mean mu as used, and the S entries of its
 // cmean column set to mu, for the matrix-core product Z^T U to be added to.
-#include <cfloat>
-
+#include "belief.h" // the clamp
 #include "logh.h"
 
 namespace {
@@ -42,10 +41,8 @@ __global__ __launch_bounds__(NEI_T) void k_lognei(NeiArgs q)
     const double inf = __longlong_as_double(0x7ff0000000000000LL), nan = __longlong_as_double(0x7ff8000000000000LL);
 
     double sd;
-    if (q.cvar) { // the clamp of gp.hpp:623; a NaN stays one
-        const double v = q.cvar[m];
-        sd = sqrt(v > DBL_EPSILON ? v : (v != v ? v : 0.0));
-    }
+    if (q.cvar)
+        sd = belief_sigma(q.cvar[m], 0.0);
     else
         sd = q.csd[m];
     const double lsd = log(sd); // (sd = 0: not used)

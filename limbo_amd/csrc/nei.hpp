@@ -1,9 +1,9 @@
 // nei.hpp — noisy expected improvement in the log domain (include/gpe_nei.h): host side.  Kernels: nei.hip.
-// A part of engine.hip's translation unit (included there, once, behind joint.hpp, kg.hpp and mes.hpp, whose helpers it shares).
+// A part of engine.hip's translation unit (included there, once, behind joint.hpp and acq.hpp, whose helpers it shares).
 #pragma once
 
 // Candidates on the device at once: U (B x chunk) and cmean (S x chunk) lie beside the chunk's own buffers
-static const int64_t kNeiChunk = 16384;
+static const int64_t kNeiChunk = kValuesChunk;
 // The tile of the solve by L_b and of the product Z^T U: B <= 1024 rows never fill the chip with 128 x 128 tiles, and a tile picked
 // by the size of each product would come from the chunk — a candidate's answer must not depend on the batch around it
 static const int kNeiTile = 64;
@@ -104,11 +104,8 @@ static int nei_impl(gpe_ctx* c, int out, const double* Xb, int64_t B, const doub
     gpe_ctx* sc = nullptr;
     if (const int e = joint_scratch(c, B, &sc))
         return e;
-    // two sets of chunk buffers in one lease of the scratch, as kg_impl's: the baseline's (resident for the call: Zt_b, mu_b) and a
-    // candidate chunk's
-    const int64_t mb_max = round_up(B, 64);
-    const int64_t mc_max = std::min<int64_t>(qt_serves(c) ? qt_rows_per_chunk(N, M) : std::min<int64_t>(nm_cols_per_chunk(c->ld, M), kKgNmChunk),
-                                             kNeiChunk);
+    // two sets of chunk buffers in one lease of the scratch: the baseline's (resident for the call: Zt_b, mu_b) and a candidate chunk's
+    const int64_t mb_max = round_up(B, 64), mc_max = cand_chunk_max(c, M, kNeiChunk);
     QtBufs bb = served_layout(c, mb_max, N), bc = served_layout(c, mc_max, N);
     const int64_t ldu = mb_max + 16; // c, then u in its place: B x mc, column-major, the baseline contiguous
     const int64_t ldcm = round_up(S, 16);
@@ -192,24 +189,8 @@ static int nei_impl(gpe_ctx* c, int out, const double* Xb, int64_t B, const doub
     for (int64_t m0 = 0; m0 < M && rc == GPE_OK; m0 += mc_max) {
         const int64_t mc = std::min<int64_t>(mc_max, M - m0);
         const int u0 = mk.mark();
-        // the chunk's head (with k^T alpha), solve and variance as a query's
-        chunk_head(c, bc, Xc + m0 * D, true, mc, true, true, nullptr, 0, mc);
-        const ZView zc = chunk_solve(c, bc, mc);
-        chunk_var(c, bc, mc, zc);
-        {
-            // c = k(Xb, Xc) - Zt_b Zt_c^T on the matrix cores, as kg_impl forms it: the tile from N alone, the k range whole
-            PhaseScope ps(c, GPE_PH_QUERY, 2.0 * (double)B * mc * N);
-            launch_build_Ks(s, bb.dQt, bb.ldq, B, bc.dQt, bc.ldq, mc, c->kp, dU, ldu);
-            GemmArgs g{};
-            g.C = dU;
-            g.ldc = ldu;
-            z_operands(g, zb, zc);
-            g.m = B;
-            g.n = mc;
-            g.k = N;
-            g.tile = qt_tile(N);
-            launch_gemm_sub(s, g);
-        }
+        const ZView zc = cand_chunk(c, bc, Xc + m0 * D, mc, true);
+        cross_cov(c, bb, zb, B, bc, zc, mc, dU, ldu); // c = k(Xb, Xc) - Zt_b Zt_c^T
         if (mean_add)
             HIPCHK(c, hipMemcpyAsync(dAdd, mean_add + m0, sizeof(double) * (size_t)mc, hipMemcpyHostToDevice, s));
         const int u1 = mk.mark();
@@ -299,12 +280,4 @@ int gpe_lognei_batch(gpe_handle c, int out, const double* Xb, int64_t B, const d
     return nei_impl(c, out, Xb, B, mean_b, jitter, Z, S, xi, Xc, M, mean_add, lognei, fplus, mu, var, cvar, cmean, ldm);
 }
 
-int gpe_nei_phase_ms(gpe_handle c, double* ms5)
-{
-    if (!c || !ms5)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int q = 0; q < 5; ++q)
-        ms5[q] = c->nei_ms[q];
-    return GPE_OK;
-}
+int gpe_nei_phase_ms(gpe_handle c, double* ms5) { return phase_ms_get(c, &gpe_ctx::nei_ms, ms5); }

@@ -177,12 +177,4 @@ int gpe_query_batch_grad(gpe_handle c, const double* Xq, int64_t M, double* kta,
     return qgrad_impl(c, Xq, M, kta, var, dkta, dvar);
 }
 
-int gpe_query_grad_phase_ms(gpe_handle c, double* ms3)
-{
-    if (!c || !ms3)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int q = 0; q < 3; ++q)
-        ms3[q] = c->qgrad_ms[q];
-    return GPE_OK;
-}
+int gpe_query_grad_phase_ms(gpe_handle c, double* ms3) { return phase_ms_get(c, &gpe_ctx::qgrad_ms, ms3); }

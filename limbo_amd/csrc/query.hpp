@@ -197,6 +197,16 @@ struct Marks {
         return t;
     }
 };
+
+// What stands behind every gpe_*_phase_ms export: the handle's record of its last call of that kind, n values, under its mutex
+template <int n> int phase_ms_get(gpe_ctx* c, double (gpe_ctx::*ms)[n], double* out)
+{
+    if (!c || !out)
+        return GPE_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    std::copy(c->*ms, c->*ms + n, out);
+    return GPE_OK;
+}
 } // namespace
 } // extern "C++"
 

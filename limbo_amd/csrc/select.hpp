@@ -148,14 +148,6 @@ int gpe_select_batch(gpe_handle c, const double* Xq, int64_t M, int q, int rule,
     return select_impl(c, Xq, M, q, rule, param, mu_q, var_add, obs_noise, distinct ? 1 : 0, idx, score, var_out, W, ldw);
 }
 
-int gpe_select_phase_ms(gpe_handle c, double* ms3)
-{
-    if (!c || !ms3)
-        return GPE_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    for (int k = 0; k < 3; ++k)
-        ms3[k] = c->select_ms[k];
-    return GPE_OK;
-}
+int gpe_select_phase_ms(gpe_handle c, double* ms3) { return phase_ms_get(c, &gpe_ctx::select_ms, ms3); }
 
 int gpe_debug_select_plan(int64_t M, int64_t N, int cus, int64_t* out, int64_t cap_rows) { return select_plan(M, N, cus, out, cap_rows); }

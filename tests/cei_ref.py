@@ -16,7 +16,7 @@ import numpy as np
 from scipy.special import erfc, log_ndtr
 
 SQRT2, SQRT2PI, LOG_SQRT2PI = math.sqrt(2.0), math.sqrt(2.0 * math.pi), 0.5 * math.log(2.0 * math.pi)
-CROSSOVER = 3.0  # the kernel's (limbo_amd/csrc/cei.hip: CEI_XC); the tests probe both sides of it
+CROSSOVER = 3.0  # the kernel's (limbo_amd/csrc/logh.h: LOGH_XC); the tests probe both sides of it
 REF_DEPTH = 400
 MAX_CONSTRAINTS = 16
 

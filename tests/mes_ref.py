@@ -13,14 +13,14 @@ Three regions (x = |g|, R(x) = Phi(-x) / phi(x), 1 / T = x + c2, c2 = 2 / (x + 3
   g > +CROSSOVER    Q = phi R,  log t = -g^2 / 2 - log sqrt(2 pi) + log B,  B = g / (2 (1 - Q)) + R (-log1p(-Q) / Q),
                     t' / t = -[1 + g (g + phi / (1 - Q))] / (2 (1 - Q) B)
   otherwise         t = g lambda / 2 - log Phi,  t' = -(lambda / 2) (1 + g (g + lambda))
-The continued fraction is taken to a depth far beyond need (REF_DEPTH); the kernel's is 60 (limbo_amd/csrc/mes.hip: MES_DEPTH)."""
+The continued fraction is taken to a depth far beyond need (REF_DEPTH); the kernel's is 60 (limbo_amd/csrc/logh.h: LOGH_DEPTH)."""
 import math
 
 import numpy as np
 from scipy.special import erfc, log_ndtr
 
 SQRT2, SQRT2PI, LOG_SQRT2PI = math.sqrt(2.0), math.sqrt(2.0 * math.pi), 0.5 * math.log(2.0 * math.pi)
-CROSSOVER = 3.0  # the kernel's (limbo_amd/csrc/mes.hip: MES_XC); the tests probe both sides of it
+CROSSOVER = 3.0  # the kernel's (limbo_amd/csrc/logh.h: LOGH_XC); the tests probe both sides of it
 REF_DEPTH = 400
 MAX_OUTPUTS = 8
 MAX_SAMPLES = 1024

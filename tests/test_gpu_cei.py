@@ -15,6 +15,7 @@ from oracle import np_oracle as O
 from tests import cei_ref as R
 from tests.test_cei_host import BAR, E_REF_CEI, NOISES, check_dropin, dropin_problem, run_driver, with_steps
 from tests.test_gpu_joint_posterior import ELL6, NOISE, problem
+from tests.test_gpu_kg import CHUNK_NM, check_second_chunk, two_chunk_model
 from tests.test_kg_host import dropin_reference
 
 pytestmark = pytest.mark.gpu
@@ -359,3 +360,18 @@ def test_search_leaves_the_plateau(tmp_path):
     print(f"logcei at the 8 starts {np.sort(lc[starts])}, plain ECI there {eci[starts]}; after the search {got['search_value'][0]:.6e}")
     assert len(lc) == 64 and np.all(np.isfinite(lc)) and np.all(eci[starts] == 0.0), "plain ECI is exactly 0 at every start"
     assert got["search_value"][0] > lc.max(), "the search climbs where the plain value is flat"
+
+
+# ------------------------------------------------------------------------------------------------ the fused call's second chunk
+def test_fused_second_chunk(engine_lib):
+    h, V, rng = two_chunk_model(engine_lib, 3)
+    add = 0.05 * rng.standard_normal((len(V), 3))
+
+    def call(sel):
+        out = h.logcei_batch(V[sel], [-0.2, 0.1], [1, 2], out0=0, f_best=0.5, with_ei=True, mean_add=add[sel], var_add=0.1)
+        assert out[0] == 0
+        return out[1:]
+
+    check_second_chunk(call, len(V))
+    assert np.all(np.isfinite(call(slice(CHUNK_NM, len(V)))[0]))
+    h.close()

@@ -17,6 +17,7 @@ from tests import ehvi_cases as C
 from tests import ehvi_ref as R
 from tests.test_ehvi_host import BAR, E_REF_EHVI, NOISES, check_dropin, rel_err, run_driver, with_steps
 from tests.test_gpu_joint_posterior import ELL6, NOISE, problem
+from tests.test_gpu_kg import CHUNK_NM, check_second_chunk, two_chunk_model
 from tests.test_kg_host import dropin_reference
 
 pytestmark = pytest.mark.gpu
@@ -291,3 +292,20 @@ def test_dropin_on_the_device(tmp_path, oracle_lib, observation):
         assert np.all(np.abs(got[key] - rv) <= bound), key
     assert np.all(np.abs(got["one"] - got["two"]) <= 2 * bound), "the two forms agree"
     assert int(got["best_one"][0]) == int(np.argmax(rv)) == int(got["best_two"][0])
+
+
+# ------------------------------------------------------------------------------------------------ 7. the fused call's second chunk
+def test_fused_second_chunk(engine_lib):
+    h, V, rng = two_chunk_model(engine_lib, 2)
+    F, ref = np.array([[-0.5, 0.8], [0.1, 0.3], [0.7, -0.4]]), (-1.5, -1.5)
+    assert R.is_prepared(F, ref)
+    add = 0.05 * rng.standard_normal((len(V), 2))
+
+    def call(sel):
+        out = h.ehvi2_batch(V[sel], F, ref, 0, 1, add[sel], 0.1)
+        assert out[0] == 0
+        return out[1:]
+
+    check_second_chunk(call, len(V))
+    assert np.any(call(slice(CHUNK_NM, len(V)))[0] > 0)
+    h.close()

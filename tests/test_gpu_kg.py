@@ -356,3 +356,49 @@ def test_dropin_host_and_device_agree(tmp_path, oracle_lib, n):
     for got in (host, dev, nat):
         assert np.max(np.abs(got["kg"] - ref)) <= E2E_BOUND and int(got["best"][0]) == int(np.argmax(ref))
     assert np.max(np.abs(host["kg"] - dev["kg"])) <= E2E_BOUND
+
+
+# ------------------------------------------------------------------------------------------------ the fused calls' second chunk
+CHUNK_NM = 8192  # candidates per chunk of a fused call in the N x M layout (fewer samples than one outer panel)
+
+
+def two_chunk_model(engine_lib, P):
+    """N = 200 samples (the N x M layout), D = 4, P outputs, SE-ARD; CHUNK_NM + 65 candidates: a fused call runs its loop twice"""
+    rng = np.random.default_rng(8192 + P)
+    N, D, M = 200, 4, CHUNK_NM + 65
+    X = rng.random((N, D))
+    Y = np.stack([np.sin(3.0 * X @ rng.random(D)) for _ in range(P)], axis=1) + 0.1 * rng.standard_normal((N, P))
+    h = _capi.Handle(engine_lib)
+    h.set_data(X, Y - Y.mean(axis=0))
+    h.set_kernel(O.SE_ARD, np.log([0.3, 0.5, 0.7, 0.9, 1.0]), 0.1)
+    assert h.compute() == 0
+    return h, rng.random((M, D)), rng
+
+
+def check_second_chunk(call, M):
+    """call(sel): every returned array of the fused call on the candidates V[sel] (with their rows of mean_add), candidates along
+    axis 0.  The whole batch's answers behind the chunk boundary are bitwise those of the same candidates asked alone, and so are
+    the candidates on either side of the boundary."""
+    assert M > CHUNK_NM
+    whole = call(slice(0, M))
+    assert all(w.shape[0] == M and not np.any(np.isnan(w)) for w in whole)
+    tail = call(slice(CHUNK_NM, M))
+    for w, t in zip(whole, tail):
+        assert np.array_equal(w[CHUNK_NM:], t), "the second chunk's candidates asked alone"
+    for m in (CHUNK_NM - 1, CHUNK_NM):
+        for w, o in zip(whole, call(slice(m, m + 1))):
+            assert np.array_equal(w[m:m + 1], o), f"candidate {m} alone"
+
+
+def test_fused_second_chunk(engine_lib):
+    h, V, rng = two_chunk_model(engine_lib, 1)
+    Xa, mu_c = rng.random((65, V.shape[1])), 0.05 * rng.standard_normal(len(V))
+
+    def call(sel):
+        rc, kg, var, cov = h.kg_batch(Xa, V[sel], 0.1, with_self=True, mu_c=mu_c[sel])
+        assert rc == 0
+        return kg, var, cov.T
+
+    check_second_chunk(call, len(V))
+    assert np.any(call(slice(CHUNK_NM, len(V)))[0] > 0)
+    h.close()

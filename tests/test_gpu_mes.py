@@ -15,6 +15,7 @@ from oracle import np_oracle as O
 from tests import mes_ref as R
 from tests.test_gpu_cei import multi_handle
 from tests.test_gpu_joint_posterior import ELL6, NOISE, problem
+from tests.test_gpu_kg import CHUNK_NM, check_second_chunk, two_chunk_model
 from tests.test_kg_host import dropin_reference
 from tests.test_mes_host import BAR, E_REF_MES, NOISES, check_dropin, dropin_problem, run_driver, with_steps
 
@@ -378,3 +379,19 @@ def test_search_leaves_the_flat_region(tmp_path):
     got = run_driver(tmp_path, 0, 0, X, Y, X[:2], 8, 5, noise_id=1, observation=1, hp=ELL6, search=1)
     assert np.all(got["host_resident"] == 0)
     check_search(got, 8, NOISES[1])
+
+
+# ------------------------------------------------------------------------------------------------ the fused call's second chunk
+def test_fused_second_chunk(engine_lib):
+    h, V, rng = two_chunk_model(engine_lib, 2)
+    ystar = 1.0 + 0.3 * np.abs(rng.standard_normal((65, 2)))
+    add = 0.05 * rng.standard_normal((len(V), 2))
+
+    def call(sel):
+        out = h.mes_batch(V[sel], ystar, mean_add=add[sel], var_add=0.1)
+        assert out[0] == 0
+        return out[1:]
+
+    check_second_chunk(call, len(V))
+    assert np.all(np.isfinite(call(slice(CHUNK_NM, len(V)))[0]))
+    h.close()

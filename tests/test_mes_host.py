@@ -55,8 +55,11 @@ def test_abi_lives_in_its_own_header(engine_lib):
     assert _capi.MES_MAX_OUTPUTS == R.MAX_OUTPUTS == 8 and _capi.MES_MAX_SAMPLES == R.MAX_SAMPLES == 1024
     assert re.search(r"#define\s+GPE_MES_MAX_OUTPUTS\s+8\b", hs) and re.search(r"#define\s+GPE_MES_MAX_SAMPLES\s+1024\b", hs)
     assert b"k_mes" in _capi.ENGINE_SO.read_bytes(), "the kernel is in the shipped code object"
-    src = (ROOT / "limbo_amd" / "csrc" / "mes.hip").read_text()
-    assert re.search(r"MES_XC\s*=\s*3\.0\b", src) and R.CROSSOVER == 3.0, "the tests probe the kernel's crossover"
+    csrc = ROOT / "limbo_amd" / "csrc"
+    src = (csrc / "mes.hip").read_text()
+    # the crossover is logh.h's, the one the kernel uses: it includes the header, branches on LOGH_XC and defines none of its own
+    assert '#include "logh.h"' in src and "LOGH_XC" in src and not re.search(r"_XC\s*=", src)
+    assert re.search(r"LOGH_XC\s*=\s*3\.0\b", (csrc / "logh.h").read_text()) and R.CROSSOVER == 3.0, "the tests probe the kernel's crossover"
 
 
 def test_argument_statuses_without_a_device(engine_lib):

@@ -17,6 +17,9 @@ drops or hands on a device buffer (lifecycle_steps); it prints the sha256 of eve
 The cases of QUERY_CASES and SPARSE_CASES are about the host side of the query family (limbo_amd/csrc/query.hpp and the calls
 built on its chunk helpers): one line per call with its launches and the sha256 of every array it returned.
 
+The cases of ACQ_CASES are about the host side of the acquisition family (limbo_amd/csrc/acq.hpp and the five calls built on it):
+one line per call, as the query cases.
+
 The case `shell` is about the handle's shell (limbo_amd/csrc/shell_layout.h: the streams, the device block and the pinned block
 that a destroyed handle leaves to the next one): three handles in a row in one process, each taking the shell of the one before,
 through every region of the two blocks (run_shell_case); one line per call, as the query cases.
@@ -78,8 +81,18 @@ SPARSE_CASES = {
     "s300": (1300, 300, 130, {}, "the transposed layout: both panel solves of the prediction"),
     "s300c": (1300, 300, 130, {"GPE_SPARSE_CHUNK": "512", "GPE_QUERY_T": "0"}, "... three chunks; transposed whatever GPE_QUERY_T says"),
 }
+# The acquisition family (limbo_amd/csrc/acq.hpp: kg, ehvi, cei, mes, nei): a fitted model (P = 4) through every fused call — with
+# everything wanted and with a strict subset, with and without the caller's means — and every call on host-supplied beliefs.
+# case: (N, candidates, profiling, environment, what it reaches)
+ACQ_CASES = {
+    "a520": (520, 70, False, {}, "the transposed layout"),
+    "a200": (200, 70, False, {}, "fewer samples than one outer panel: N x M"),
+    "a200x": (200, 8192 + 65, False, {}, "N x M, the fused calls' loop twice"),
+    "aprof": (520, 70, True, {}, "profiling on: the timers' branches"),
+    "aprofnm": (200, 70, True, {}, "profiling on in the N x M layout"),
+}
 SHELL_CASES = {"shell": ({}, "three handles on one pooled shell: stepped panels with head copy, one-launch panels, the small path")}
-ALL_CASES = {**CASES, **QUERY_CASES, **SPARSE_CASES, **SHELL_CASES}
+ALL_CASES = {**CASES, **QUERY_CASES, **SPARSE_CASES, **ACQ_CASES, **SHELL_CASES}
 D = 4
 NOISE = 0.01
 CHILD_TIMEOUT_S = 180
@@ -257,6 +270,77 @@ def run_sparse_case(np, _capi, name):
         h.close()
 
 
+def run_acq_case(np, _capi, name):
+    N, M, prof, _, _ = ACQ_CASES[name]
+    P, A, B, S, K = 4, 33, 20, 65, 65
+    lib = _capi.load_engine()
+    X, Y = problem(np, N, P, 6000)
+    rng = np.random.default_rng(6001)
+    Xc, Xa, Xb = (rng.uniform(-2.0, 2.0, (n, D)) for n in (M, A, B))
+    h = _capi.Handle(lib, 0)
+    h.set_data(X, Y)
+    h.set_kernel(_capi.KERNEL_SE_ARD, 0.1 * np.arange(D + 1) - 0.2, NOISE)
+    h.set_profiling(prof)
+    assert h.compute() == 0
+
+    def call(label, fn, names, times=None):
+        res, launches = traced(lib, fn)
+        report(np, name, label, launches, dict(zip(names, res)), times() if times and prof else None)
+
+    add = 0.05 * rng.standard_normal((M, P))  # the caller's means, column j for belief j
+    mu, sd = rng.standard_normal((M, P)), 0.1 + rng.random((M, P))  # host-supplied beliefs
+    # the knowledge gradient
+    names = ("status", "kg", "var", "cov")
+    mu_a, mu_c = rng.standard_normal(A), rng.standard_normal(M)
+    call("kg_batch", lambda: h.kg_batch(Xa, Xc, 0.1), names, h.kg_phase_ms)
+    call("kg_batch.self", lambda: h.kg_batch(Xa, Xc, 0.1, with_self=True), names, h.kg_phase_ms)
+    call("kg_batch.self.mu", lambda: h.kg_batch(Xa, Xc, 0.1, with_self=True, mu_a=mu_a, mu_c=mu_c), names, h.kg_phase_ms)
+    call("kg_batch.mu.kg", lambda: h.kg_batch(Xa, Xc, 0.1, mu_a=mu_a, mu_c=mu_c, want=("kg",)), names, h.kg_phase_ms)
+    call("kg_batch.self.var_cov", lambda: h.kg_batch(Xa, Xc, 0.1, with_self=True, want=("var", "cov")), names, h.kg_phase_ms)
+    call("kg_envelope", lambda: h.kg_envelope(mu_a, rng.standard_normal((A, M)), ldb=A + 3), ("status", "kg", "nseg"))
+    # the expected hypervolume improvement of outputs (2, 0)
+    ref = (float(Y[:, 2].min()) - 0.1, float(Y[:, 0].min()) - 0.1)
+    rc, F = _capi.ehvi2_front(Y[:, [2, 0]], ref)
+    assert rc == 0 and len(F) >= 2
+    names = ("status", "ehvi", "partials", "mu", "var")
+    call("ehvi2_values", lambda: h.ehvi2_values(F, ref, mu[:, 0], sd[:, 0], mu[:, 1], sd[:, 1]), ("status", "ehvi", "partials"))
+    call("ehvi2_values.ehvi", lambda: h.ehvi2_values(F, ref, mu[:, 0], sd[:, 0], mu[:, 1], sd[:, 1], want_partials=False), ("status", "ehvi", "partials"))
+    call("ehvi2_batch.add", lambda: h.ehvi2_batch(Xc, F, ref, 2, 0, add[:, :2], 0.1), names, h.ehvi_phase_ms)
+    call("ehvi2_batch", lambda: h.ehvi2_batch(Xc, F, ref, 2, 0), names, h.ehvi_phase_ms)
+    call("ehvi2_batch.partials_var", lambda: h.ehvi2_batch(Xc, F, ref, 2, 0, add[:, :2], 0.1, want=("partials", "var")), names, h.ehvi_phase_ms)
+    # constrained expected improvement: the objective output 1, constraints on outputs (3, 0, 2)
+    thr = np.array([-0.3, 0.0, 0.2])
+    names = ("status", "logcei", "terms", "partials", "mu", "var")
+    for with_ei, C in ((1, 3), (1, 0), (0, 3)):
+        tag = f".ei{with_ei}.c{C}"
+        vals = lambda want: h.logcei_values(thr[:C], mu[:, 1:1 + C], sd[:, 1:1 + C], mu[:, 0], sd[:, 0], f_best=0.5, with_ei=with_ei, want=want)
+        call("logcei_values" + tag, lambda: vals(("terms", "partials")), names[:4])
+        call("logcei_values" + tag + ".partials", lambda: vals(("partials",)), names[:4])
+    for with_ei, C in ((1, 3), (1, 0), (0, 3), (0, 0)):
+        tag = f".ei{with_ei}.c{C}"
+        fused = lambda mean_add, **kw: h.logcei_batch(Xc, thr[:C], [3, 0, 2][:C], out0=1, f_best=0.5, with_ei=with_ei, mean_add=mean_add, **kw)
+        call("logcei_batch" + tag + ".add", lambda: fused(add[:, :1 + C], var_add=0.1), names, h.cei_phase_ms)
+        call("logcei_batch" + tag, lambda: fused(None), names, h.cei_phase_ms)
+        call("logcei_batch" + tag + ".terms_mu", lambda: fused(add[:, :1 + C], var_add=0.1, want=("terms", "mu")), names, h.cei_phase_ms)
+    # max-value entropy search over outputs (2, 0)
+    ystar = 1.0 + 0.3 * np.abs(rng.standard_normal((K, 2)))
+    names = ("status", "logmes", "terms", "partials", "mu", "var")
+    call("mes_values", lambda: h.mes_values(ystar, mu[:, :2], sd[:, :2]), names[:4])
+    call("mes_values.terms", lambda: h.mes_values(ystar, mu[:, :2], sd[:, :2], want=("terms",)), names[:4])
+    call("mes_batch.add", lambda: h.mes_batch(Xc, ystar, [2, 0], add[:, :2], 0.1), names, h.mes_phase_ms)
+    call("mes_batch", lambda: h.mes_batch(Xc, ystar, [2, 0]), names, h.mes_phase_ms)
+    call("mes_batch.partials_var", lambda: h.mes_batch(Xc, ystar, [2, 0], add[:, :2], 0.1, want=("partials", "var")), names, h.mes_phase_ms)
+    # noisy expected improvement of output 1 over a baseline of B points
+    Z, mean_b = rng.standard_normal((B, S)), 0.05 * rng.standard_normal(B)
+    names = ("status", "lognei", "fplus", "mu", "var", "cvar", "cmean")
+    call("lognei_values", lambda: h.lognei_values(rng.standard_normal(S), rng.standard_normal((S, M)), sd[:, 0]), ("status", "lognei", "terms"))
+    call("lognei_values.lognei", lambda: h.lognei_values(rng.standard_normal(S), rng.standard_normal((S, M)), sd[:, 0], want=()), ("status", "lognei", "terms"))
+    call("lognei_batch.add", lambda: h.lognei_batch(Xc, Xb, Z, 1, 1e-6, mean_b=mean_b, mean_add=add[:, 0]), names, h.nei_phase_ms)
+    call("lognei_batch", lambda: h.lognei_batch(Xc, Xb, Z, 1, 1e-6), names, h.nei_phase_ms)
+    call("lognei_batch.mu_cvar", lambda: h.lognei_batch(Xc, Xb, Z, 1, 1e-6, mean_b=mean_b, mean_add=add[:, 0], want=("mu", "cvar")), names, h.nei_phase_ms)
+    h.close()
+
+
 def run_shell_case(np, _capi, name):
     """The switches of the panel code are read by gpe_create: set between the creates, they differ from handle to handle."""
     lib = _capi.load_engine()
@@ -316,6 +400,8 @@ def run_case(name, root):
         return run_query_case(np, _capi, name)
     if name in SPARSE_CASES:
         return run_sparse_case(np, _capi, name)
+    if name in ACQ_CASES:
+        return run_acq_case(np, _capi, name)
     if name in SHELL_CASES:
         return run_shell_case(np, _capi, name)
     N, P, _, _ = CASES[name]
