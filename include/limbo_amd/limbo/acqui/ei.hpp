@@ -13,7 +13,7 @@
 #include <tuple>
 #include <vector>
 #include <Eigen/Core>
-#include <limbo/acqui/afun_gradient.hpp>
+#include <limbo/acqui/beliefs.hpp>
 #include <limbo/opt/optimizer.hpp>
 #include <limbo/tools/macros.hpp>
 namespace limbo {
@@ -34,25 +34,20 @@ namespace limbo {
             opt::eval_t operator()(const Eigen::VectorXd& v, const AggregatorFunction& afun, bool gradient)
             {
                 if (gradient)
-                    return _one_with_gradient(v, afun, limbo_amd::afun_differentiable<AggregatorFunction>());
+                    return limbo_amd::beliefs::one_with_gradient(*this, v, afun,
+                        "limbo_amd: acqui::EI with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
                 Eigen::VectorXd mu;
                 double sigma_sq;
                 std::tie(mu, sigma_sq) = _model.query(v);
-                return opt::no_grad(_value(afun(mu), sigma_sq, afun));
+                return opt::no_grad(_value(afun(mu), std::sqrt(sigma_sq), afun));
             }
             template <typename AggregatorFunction>
             std::vector<double> batch(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun)
             {
-                Eigen::MatrixXd mu;
-                Eigen::VectorXd s2;
-                _model.query_batch(points, mu, s2);
-                std::vector<double> out(points.size());
-                for (size_t m = 0; m < points.size(); ++m) {
-                    Eigen::VectorXd row(mu.cols());
-                    for (int p = 0; p < (int)mu.cols(); ++p)
-                        row(p) = mu(m, p);
-                    out[m] = _value(afun(row), s2(m), afun);
-                }
+                std::vector<double> fmu, sigma, out(points.size());
+                limbo_amd::beliefs::aggregated(_model, points, afun, true, fmu, sigma);
+                for (size_t m = 0; m < points.size(); ++m)
+                    out[m] = _value(fmu[m], sigma[m], afun);
                 return out;
             }
 
@@ -63,30 +58,21 @@ namespace limbo {
             void batch_grad(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun, std::vector<double>& values,
                 std::vector<Eigen::VectorXd>& grads)
             {
-                Eigen::MatrixXd mu, ds2;
-                Eigen::VectorXd s2;
-                std::vector<Eigen::MatrixXd> dmu;
-                _model.query_grad_batch(points, mu, s2, dmu, ds2);
+                std::vector<double> fmu, sigma;
+                std::vector<Eigen::VectorXd> gmu;
+                Eigen::MatrixXd ds2;
+                limbo_amd::beliefs::aggregated_grad(_model, points, afun, true, fmu, sigma, gmu, ds2);
                 values.resize(points.size());
                 grads.resize(points.size());
                 for (size_t m = 0; m < points.size(); ++m) {
-                    Eigen::VectorXd row(mu.cols());
-                    for (int p = 0; p < (int)mu.cols(); ++p)
-                        row(p) = mu(m, p);
-                    const double fmu = afun(row), sigma = std::sqrt(s2(m));
-                    values[m] = _value(fmu, s2(m), afun);
+                    values[m] = _value(fmu[m], sigma[m], afun);
                     Eigen::VectorXd g = Eigen::VectorXd::Zero(ds2.cols());
-                    if (!(sigma < 1e-10 || _model.samples().size() < 1)) {
-                        const Eigen::VectorXd da = limbo_amd::afun_gradient(afun, row);
-                        const double Z = (fmu - _f_max - Params::acqui_ei::jitter()) / sigma;
+                    if (!(sigma[m] < 1e-10 || _model.samples().size() < 1)) {
+                        const double Z = (fmu[m] - _f_max - Params::acqui_ei::jitter()) / sigma[m];
                         const double phi = std::exp(-0.5 * Z * Z) / std::sqrt(2.0 * M_PI);
                         const double Phi = 0.5 * std::erfc(-Z / std::sqrt(2));
-                        for (int d = 0; d < (int)ds2.cols(); ++d) {
-                            double s = 0.0;
-                            for (int p = 0; p < (int)mu.cols(); ++p)
-                                s += da(p) * dmu[m](p, d);
-                            g(d) = Phi * s + phi * ds2(m, d) / (2.0 * sigma);
-                        }
+                        for (int d = 0; d < (int)ds2.cols(); ++d)
+                            g(d) = Phi * gmu[m](d) + phi * ds2(m, d) / (2.0 * sigma[m]);
                     }
                     grads[m] = g;
                 }
@@ -97,25 +83,9 @@ namespace limbo {
             int _nb_samples;
             double _f_max;
 
-            // operator() with gradient == true: batch_grad() for one point (see acqui/ucb.hpp)
             template <typename AggregatorFunction>
-            opt::eval_t _one_with_gradient(const Eigen::VectorXd& v, const AggregatorFunction& afun, std::true_type)
+            double _value(double fmu, double sigma, const AggregatorFunction& afun)
             {
-                std::vector<double> val;
-                std::vector<Eigen::VectorXd> gr;
-                batch_grad(std::vector<Eigen::VectorXd>(1, v), afun, val, gr);
-                return opt::eval_t{val[0], opt::eval_t::second_type(gr[0])};
-            }
-            template <typename AggregatorFunction>
-            opt::eval_t _one_with_gradient(const Eigen::VectorXd&, const AggregatorFunction&, std::false_type)
-            {
-                throw std::logic_error("limbo_amd: acqui::EI with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
-            }
-
-            template <typename AggregatorFunction>
-            double _value(double fmu, double sigma_sq, const AggregatorFunction& afun)
-            {
-                const double sigma = std::sqrt(sigma_sq);
                 if (sigma < 1e-10 || _model.samples().size() < 1)
                     return 0.0;
                 if (_nb_samples != _model.nb_samples()) { // best predicted observation so far
@@ -123,12 +93,8 @@ namespace limbo {
                     Eigen::VectorXd s2;
                     _model.query_batch(_model.samples(), mu, s2);
                     double best = -std::numeric_limits<double>::infinity();
-                    for (int i = 0; i < (int)mu.rows(); ++i) {
-                        Eigen::VectorXd row(mu.cols());
-                        for (int p = 0; p < (int)mu.cols(); ++p)
-                            row(p) = mu(i, p);
-                        best = std::max(best, (double)afun(row));
-                    }
+                    for (int i = 0; i < (int)mu.rows(); ++i)
+                        best = std::max(best, (double)afun(limbo_amd::beliefs::row_of(mu, (size_t)i)));
                     _nb_samples = _model.nb_samples();
                     _f_max = best;
                 }

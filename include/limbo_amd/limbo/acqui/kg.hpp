@@ -12,6 +12,7 @@
 #include <Eigen/Core>
 
 #include <limbo/acqui/batch_select.hpp>
+#include <limbo/acqui/beliefs.hpp>
 
 namespace limbo_amd {
     /// kg[m] of every candidate over `alternatives`; afun(mu) is the mean that is maximised.  with_self: the candidate itself is one
@@ -36,12 +37,7 @@ namespace limbo_amd {
     int64_t kg_best(const Model& model, const std::vector<Eigen::VectorXd>& alternatives, const std::vector<Eigen::VectorXd>& candidates,
         const AggregatorFunction& afun = AggregatorFunction(), bool with_self = true)
     {
-        const std::vector<double> kg = kg_batch<Params>(model, alternatives, candidates, afun, with_self);
-        int64_t best = -1;
-        for (size_t m = 0; m < kg.size(); ++m)
-            if (best < 0 || kg[m] > kg[(size_t)best])
-                best = (int64_t)m;
-        return best;
+        return beliefs::first_argmax(kg_batch<Params>(model, alternatives, candidates, afun, with_self));
     }
 } // namespace limbo_amd
 #endif

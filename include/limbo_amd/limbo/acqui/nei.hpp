@@ -15,6 +15,7 @@
 
 #include <Eigen/Core>
 
+#include <limbo/acqui/beliefs.hpp>
 #include <limbo/opt/optimizer.hpp>
 
 #include "../../../gpe_nei.h"
@@ -103,14 +104,7 @@ namespace limbo_amd {
         return v;
     }
     /// the index of the largest value (the lowest one on exact ties; NaN never wins), -1 without candidates
-    inline int64_t lognei_best(const std::vector<double>& v)
-    {
-        int64_t best = -1;
-        for (size_t m = 0; m < v.size(); ++m)
-            if (best < 0 || v[m] > v[(size_t)best])
-                best = (int64_t)m;
-        return best;
-    }
+    inline int64_t lognei_best(const std::vector<double>& v) { return beliefs::first_argmax(v); }
     template <typename Params, typename Model>
     int64_t lognei_best(const Model& model, const std::vector<Eigen::VectorXd>& candidates, const std::vector<Eigen::VectorXd>& baseline, int S,
         uint64_t seed, double jitter = 1e-6, double xi = 0.0, int out = 0)

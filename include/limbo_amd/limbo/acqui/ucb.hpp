@@ -12,7 +12,7 @@
 #include <tuple>
 #include <vector>
 #include <Eigen/Core>
-#include <limbo/acqui/afun_gradient.hpp>
+#include <limbo/acqui/beliefs.hpp>
 #include <limbo/opt/optimizer.hpp>
 #include <limbo/tools/macros.hpp>
 namespace limbo {
@@ -33,7 +33,8 @@ namespace limbo {
             opt::eval_t operator()(const Eigen::VectorXd& v, const AggregatorFunction& afun, bool gradient) const
             {
                 if (gradient)
-                    return _one_with_gradient(v, afun, limbo_amd::afun_differentiable<AggregatorFunction>());
+                    return limbo_amd::beliefs::one_with_gradient(*this, v, afun,
+                        "limbo_amd: acqui::UCB with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
                 Eigen::VectorXd mu;
                 double sigma;
                 std::tie(mu, sigma) = _model.query(v);
@@ -44,16 +45,10 @@ namespace limbo {
             template <typename AggregatorFunction>
             std::vector<double> batch(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun) const
             {
-                Eigen::MatrixXd mu;
-                Eigen::VectorXd s2;
-                _model.query_batch(points, mu, s2);
-                std::vector<double> out(points.size());
-                for (size_t m = 0; m < points.size(); ++m) {
-                    Eigen::VectorXd row(mu.cols());
-                    for (int p = 0; p < (int)mu.cols(); ++p)
-                        row(p) = mu(m, p);
-                    out[m] = afun(row) + Params::acqui_ucb::alpha() * std::sqrt(s2(m));
-                }
+                std::vector<double> fmu, sigma, out(points.size());
+                limbo_amd::beliefs::aggregated(_model, points, afun, true, fmu, sigma);
+                for (size_t m = 0; m < points.size(); ++m)
+                    out[m] = fmu[m] + Params::acqui_ucb::alpha() * sigma[m];
                 return out;
             }
 
@@ -64,48 +59,23 @@ namespace limbo {
             void batch_grad(const std::vector<Eigen::VectorXd>& points, const AggregatorFunction& afun, std::vector<double>& values,
                 std::vector<Eigen::VectorXd>& grads) const
             {
-                Eigen::MatrixXd mu, ds2;
-                Eigen::VectorXd s2;
-                std::vector<Eigen::MatrixXd> dmu;
-                _model.query_grad_batch(points, mu, s2, dmu, ds2);
+                std::vector<double> fmu, sigma;
+                std::vector<Eigen::VectorXd> gmu;
+                Eigen::MatrixXd ds2;
+                limbo_amd::beliefs::aggregated_grad(_model, points, afun, true, fmu, sigma, gmu, ds2);
                 values.resize(points.size());
                 grads.resize(points.size());
                 for (size_t m = 0; m < points.size(); ++m) {
-                    Eigen::VectorXd row(mu.cols());
-                    for (int p = 0; p < (int)mu.cols(); ++p)
-                        row(p) = mu(m, p);
-                    const double sigma = std::sqrt(s2(m));
-                    values[m] = afun(row) + Params::acqui_ucb::alpha() * sigma;
-                    const Eigen::VectorXd da = limbo_amd::afun_gradient(afun, row);
+                    values[m] = fmu[m] + Params::acqui_ucb::alpha() * sigma[m];
                     Eigen::VectorXd g(ds2.cols());
-                    for (int d = 0; d < (int)ds2.cols(); ++d) {
-                        double s = 0.0;
-                        for (int p = 0; p < (int)mu.cols(); ++p)
-                            s += da(p) * dmu[m](p, d);
-                        g(d) = s + (sigma > 0 ? Params::acqui_ucb::alpha() / (2.0 * sigma) * ds2(m, d) : 0.0);
-                    }
+                    for (int d = 0; d < (int)ds2.cols(); ++d)
+                        g(d) = gmu[m](d) + (sigma[m] > 0 ? Params::acqui_ucb::alpha() / (2.0 * sigma[m]) * ds2(m, d) : 0.0);
                     grads[m] = g;
                 }
             }
 
         protected:
             const Model& _model;
-
-            // operator() with gradient == true: batch_grad() for one point.  An aggregator without a derivative (limbo_amd::
-            // afun_differentiable) keeps compiling for gradient == false and throws here; batch_grad() itself does not compile.
-            template <typename AggregatorFunction>
-            opt::eval_t _one_with_gradient(const Eigen::VectorXd& v, const AggregatorFunction& afun, std::true_type) const
-            {
-                std::vector<double> val;
-                std::vector<Eigen::VectorXd> gr;
-                batch_grad(std::vector<Eigen::VectorXd>(1, v), afun, val, gr);
-                return opt::eval_t{val[0], opt::eval_t::second_type(gr[0])};
-            }
-            template <typename AggregatorFunction>
-            opt::eval_t _one_with_gradient(const Eigen::VectorXd&, const AggregatorFunction&, std::false_type) const
-            {
-                throw std::logic_error("limbo_amd: acqui::UCB with gradient: the aggregator needs a member gradient(mu) (or use limbo_amd::FirstElem)");
-            }
         };
     } // namespace acqui
 } // namespace limbo

@@ -63,9 +63,9 @@ namespace limbo {
                     const std::vector<double> thr(1, 1.0);
                     std::vector<double> mu0(M), s0(M), mu_c(M), s_c(M), v;
                     for (size_t m = 0; m < M; ++m) {
-                        mu0[m] = afun(limbo_amd::cei_detail::row_of(mu, m));
+                        mu0[m] = afun(limbo_amd::beliefs::row_of(mu, m));
                         s0[m] = std::sqrt(s2(m));
-                        mu_c[m] = afun(limbo_amd::cei_detail::row_of(cmu, m));
+                        mu_c[m] = afun(limbo_amd::beliefs::row_of(cmu, m));
                         s_c[m] = std::sqrt(cs2(m));
                         if (s_c[m] < 1e-10 || no_constraint_data) { // the reference's P = 1: a constraint met without uncertainty
                             mu_c[m] = 1.0;
@@ -96,7 +96,7 @@ namespace limbo {
                     _model.query_batch(_model.samples(), mu, s2);
                     double best = -std::numeric_limits<double>::infinity();
                     for (int i = 0; i < (int)mu.rows(); ++i)
-                        best = std::max(best, (double)afun(limbo_amd::cei_detail::row_of(mu, (size_t)i)));
+                        best = std::max(best, (double)afun(limbo_amd::beliefs::row_of(mu, (size_t)i)));
                     _nb_samples = _model.nb_samples();
                     _f_max = best;
                 }

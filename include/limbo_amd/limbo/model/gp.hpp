@@ -611,38 +611,23 @@ namespace limbo {
                 const double* ref, int out1, int out2, bool observation, std::vector<double>& ehvi, std::vector<double>* partials = nullptr) const
             {
                 const int64_t M = candidates.size(), n = (int64_t)front.size() / 2;
-                if (front.size() % 2 != 0 || out1 == out2 || out1 < 0 || out2 < 0 || out1 >= _dim_out || out2 >= _dim_out || !ref
-                    || n > GPE_EHVI_MAX_FRONT || gpe_ehvi2_values(nullptr, front.data(), n, ref, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr) != GPE_OK)
+                const std::vector<int> outs{out1, out2};
+                if (front.size() % 2 != 0 || !_outputs_ok(outs) || !ref || n > GPE_EHVI_MAX_FRONT
+                    || gpe_ehvi2_values(nullptr, front.data(), n, ref, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr) != GPE_OK)
                     throw std::invalid_argument("limbo_amd: expected_hypervolume_improvement(): bad argument (include/gpe_ehvi.h)");
-                ehvi.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign((size_t)(4 * M), 0.0);
+                _zeroed(M, ehvi, partials, 4, nullptr, 0);
                 if (M == 0)
                     return;
-                const double noise = _kernel_function.noise();
                 if (_joint_on_host(M)) {
-                    Eigen::MatrixXd mu;
-                    Eigen::VectorXd s2;
-                    query_batch(candidates, mu, s2);
-                    std::vector<double> m1((size_t)M), m2((size_t)M), sd((size_t)M);
-                    for (int64_t m = 0; m < M; ++m) {
-                        m1[(size_t)m] = mu(m, out1);
-                        m2[(size_t)m] = mu(m, out2);
-                        sd[(size_t)m] = std::sqrt(observation ? s2(m) : std::max(s2(m) - noise, 0.0));
-                    }
-                    limbo_amd::ehvi_host::strip_sums(front.data(), n, ref, m1.data(), sd.data(), m2.data(), sd.data(), M, ehvi.data(),
-                        partials ? partials->data() : nullptr);
+                    std::vector<double> mu, sd;
+                    _beliefs_of(candidates, outs, observation, mu, sd);
+                    limbo_amd::ehvi_host::strip_sums(front.data(), n, ref, mu.data(), sd.data(), mu.data() + M, sd.data() + M, M, ehvi.data(),
+                        _data(partials));
                     return;
                 }
-                const std::vector<double> Xc = _joint_points(candidates);
-                std::vector<double> add((size_t)(2 * M));
-                for (int64_t m = 0; m < M; ++m) {
-                    const Eigen::VectorXd mv = _mean_function(candidates[(size_t)m], *this);
-                    add[(size_t)m] = mv(out1);
-                    add[(size_t)(M + m)] = mv(out2);
-                }
-                _eng.check(gpe_ehvi2_batch(_eng.get(), out1, out2, Xc.data(), M, add.data(), observation ? noise : 0.0, front.data(), n, ref,
-                               ehvi.data(), partials ? partials->data() : nullptr, nullptr, nullptr),
+                const std::vector<double> Xc = _joint_points(candidates), add = _mean_add(candidates, outs);
+                _eng.check(gpe_ehvi2_batch(_eng.get(), out1, out2, Xc.data(), M, add.data(), observation ? _kernel_function.noise() : 0.0, front.data(), n,
+                               ref, ehvi.data(), _data(partials), nullptr, nullptr),
                     "gpe_ehvi2_batch");
             }
             /// Does this model hold an engine handle a caller's own beliefs can be scored through (ehvi2_values)?
@@ -655,11 +640,9 @@ namespace limbo {
                 const std::vector<double>& mu2, const std::vector<double>& s2, std::vector<double>& ehvi, std::vector<double>* partials = nullptr) const
             {
                 const int64_t M = mu1.size();
-                ehvi.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign((size_t)(4 * M), 0.0);
+                _zeroed(M, ehvi, partials, 4, nullptr, 0);
                 _eng.check(gpe_ehvi2_values(_eng.get(), front.data(), (int64_t)front.size() / 2, ref, mu1.data(), s1.data(), mu2.data(), s2.data(), M,
-                               ehvi.data(), partials ? partials->data() : nullptr),
+                               ehvi.data(), _data(partials)),
                     "gpe_ehvi2_values");
             }
 
@@ -678,52 +661,24 @@ namespace limbo {
             {
                 const int64_t M = candidates.size();
                 const int C = (int)con_outs.size();
-                bool ok = thr.size() == con_outs.size() && C <= GPE_CEI_MAX_CONSTRAINTS && out0 >= 0 && out0 < _dim_out
-                    && gpe_logcei_values(nullptr, with_ei, f_best, xi, C, thr.data(), nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr) == GPE_OK;
-                for (int k = 0; ok && k < C; ++k) {
-                    ok = con_outs[k] >= 0 && con_outs[k] < _dim_out && con_outs[k] != out0;
-                    for (int j = 0; ok && j < k; ++j)
-                        ok = con_outs[j] != con_outs[k];
-                }
-                if (!ok)
+                std::vector<int> outs(1, out0);
+                outs.insert(outs.end(), con_outs.begin(), con_outs.end());
+                if (thr.size() != con_outs.size() || C > GPE_CEI_MAX_CONSTRAINTS || !_outputs_ok(outs)
+                    || gpe_logcei_values(nullptr, with_ei, f_best, xi, C, thr.data(), nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr) != GPE_OK)
                     throw std::invalid_argument("limbo_amd: log_constrained_ei(): bad argument (include/gpe_cei.h)");
-                const size_t B = (size_t)(1 + C);
-                logcei.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign(2 * B * (size_t)M, 0.0);
-                if (terms)
-                    terms->assign(B * (size_t)M, 0.0);
+                _zeroed(M, logcei, partials, 2 * outs.size(), terms, outs.size());
                 if (M == 0)
                     return;
-                const double noise = _kernel_function.noise();
-                if (_joint_on_host(M)) {
-                    Eigen::MatrixXd mu;
-                    Eigen::VectorXd s2;
-                    query_batch(candidates, mu, s2);
-                    std::vector<double> m0((size_t)M), sd((size_t)M), mc((size_t)M * C), sc((size_t)M * C);
-                    for (int64_t m = 0; m < M; ++m) {
-                        m0[(size_t)m] = mu(m, out0);
-                        sd[(size_t)m] = std::sqrt(observation ? s2(m) : std::max(s2(m) - noise, 0.0));
-                        for (int k = 0; k < C; ++k) {
-                            mc[(size_t)(m + M * k)] = mu(m, con_outs[k]);
-                            sc[(size_t)(m + M * k)] = sd[(size_t)m];
-                        }
-                    }
-                    limbo_amd::cei_host::values(with_ei, f_best, xi, C, thr.data(), m0.data(), sd.data(), mc.data(), sc.data(), M, logcei.data(),
-                        terms ? terms->data() : nullptr, partials ? partials->data() : nullptr);
+                if (_joint_on_host(M)) { // the objective's belief is column 0, the constraints' the columns behind it
+                    std::vector<double> mu, sd;
+                    _beliefs_of(candidates, outs, observation, mu, sd);
+                    limbo_amd::cei_host::values(with_ei, f_best, xi, C, thr.data(), mu.data(), sd.data(), mu.data() + M, sd.data() + M, M, logcei.data(),
+                        _data(terms), _data(partials));
                     return;
                 }
-                const std::vector<double> Xc = _joint_points(candidates);
-                std::vector<double> add(B * (size_t)M);
-                for (int64_t m = 0; m < M; ++m) {
-                    const Eigen::VectorXd mv = _mean_function(candidates[(size_t)m], *this);
-                    add[(size_t)m] = mv(out0);
-                    for (int k = 0; k < C; ++k)
-                        add[(size_t)(M * (1 + k) + m)] = mv(con_outs[k]);
-                }
+                const std::vector<double> Xc = _joint_points(candidates), add = _mean_add(candidates, outs);
                 _eng.check(gpe_logcei_batch(_eng.get(), with_ei, out0, f_best, xi, C, con_outs.data(), thr.data(), Xc.data(), M, add.data(),
-                               observation ? noise : 0.0, logcei.data(), terms ? terms->data() : nullptr, partials ? partials->data() : nullptr,
-                               nullptr, nullptr),
+                               observation ? _kernel_function.noise() : 0.0, logcei.data(), _data(terms), _data(partials), nullptr, nullptr),
                     "gpe_logcei_batch");
             }
             /// gpe_logcei_values through this model's engine handle (has_engine()): beliefs the caller computed (mu_c, s_c: M x C
@@ -733,14 +688,9 @@ namespace limbo {
                 std::vector<double>* partials = nullptr, std::vector<double>* terms = nullptr) const
             {
                 const int64_t M = mu0.size();
-                const size_t B = 1 + thr.size();
-                logcei.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign(2 * B * (size_t)M, 0.0);
-                if (terms)
-                    terms->assign(B * (size_t)M, 0.0);
+                _zeroed(M, logcei, partials, 2 * (1 + thr.size()), terms, 1 + thr.size());
                 _eng.check(gpe_logcei_values(_eng.get(), with_ei, f_best, xi, (int)thr.size(), thr.data(), mu0.data(), s0.data(), mu_c.data(), s_c.data(),
-                               M, logcei.data(), terms ? terms->data() : nullptr, partials ? partials->data() : nullptr),
+                               M, logcei.data(), _data(terms), _data(partials)),
                     "gpe_logcei_values");
             }
 
@@ -758,46 +708,21 @@ namespace limbo {
                 const int64_t M = candidates.size();
                 const int J = (int)outs.size();
                 const int K = J > 0 ? (int)(ystar.size() / (size_t)J) : 0;
-                bool ok = J >= 1 && (size_t)K * (size_t)J == ystar.size()
-                    && gpe_mes_values(nullptr, J, K, ystar.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr) == GPE_OK;
-                for (int j = 0; ok && j < J; ++j) {
-                    ok = outs[j] >= 0 && outs[j] < _dim_out;
-                    for (int i = 0; ok && i < j; ++i)
-                        ok = outs[i] != outs[j];
-                }
-                if (!ok)
+                if (J < 1 || (size_t)K * (size_t)J != ystar.size() || !_outputs_ok(outs)
+                    || gpe_mes_values(nullptr, J, K, ystar.data(), nullptr, nullptr, 0, nullptr, nullptr, nullptr) != GPE_OK)
                     throw std::invalid_argument("limbo_amd: max_value_entropy(): bad argument (include/gpe_mes.h)");
-                logmes.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign(2 * (size_t)J * (size_t)M, 0.0);
-                if (terms)
-                    terms->assign((size_t)J * (size_t)M, 0.0);
+                _zeroed(M, logmes, partials, 2 * (size_t)J, terms, (size_t)J);
                 if (M == 0)
                     return;
-                const double noise = _kernel_function.noise();
                 if (_joint_on_host(M)) {
-                    Eigen::MatrixXd mu;
-                    Eigen::VectorXd s2;
-                    query_batch(candidates, mu, s2);
-                    std::vector<double> mj((size_t)M * J), sj((size_t)M * J);
-                    for (int64_t m = 0; m < M; ++m)
-                        for (int j = 0; j < J; ++j) {
-                            mj[(size_t)(m + M * j)] = mu(m, outs[j]);
-                            sj[(size_t)(m + M * j)] = std::sqrt(observation ? s2(m) : std::max(s2(m) - noise, 0.0));
-                        }
-                    limbo_amd::mes_host::values(J, K, ystar.data(), mj.data(), sj.data(), M, logmes.data(), terms ? terms->data() : nullptr,
-                        partials ? partials->data() : nullptr);
+                    std::vector<double> mu, sd;
+                    _beliefs_of(candidates, outs, observation, mu, sd);
+                    limbo_amd::mes_host::values(J, K, ystar.data(), mu.data(), sd.data(), M, logmes.data(), _data(terms), _data(partials));
                     return;
                 }
-                const std::vector<double> Xc = _joint_points(candidates);
-                std::vector<double> add((size_t)J * (size_t)M);
-                for (int64_t m = 0; m < M; ++m) {
-                    const Eigen::VectorXd mv = _mean_function(candidates[(size_t)m], *this);
-                    for (int j = 0; j < J; ++j)
-                        add[(size_t)(M * j + m)] = mv(outs[j]);
-                }
-                _eng.check(gpe_mes_batch(_eng.get(), J, outs.data(), K, ystar.data(), Xc.data(), M, add.data(), observation ? noise : 0.0, logmes.data(),
-                               terms ? terms->data() : nullptr, partials ? partials->data() : nullptr, nullptr, nullptr),
+                const std::vector<double> Xc = _joint_points(candidates), add = _mean_add(candidates, outs);
+                _eng.check(gpe_mes_batch(_eng.get(), J, outs.data(), K, ystar.data(), Xc.data(), M, add.data(), observation ? _kernel_function.noise() : 0.0,
+                               logmes.data(), _data(terms), _data(partials), nullptr, nullptr),
                     "gpe_mes_batch");
             }
             /// gpe_mes_values through this model's engine handle (has_engine()): beliefs the caller computed (mu, s: M x J column-major)
@@ -805,13 +730,9 @@ namespace limbo {
                 std::vector<double>& logmes, std::vector<double>* terms = nullptr, std::vector<double>* partials = nullptr) const
             {
                 const int64_t M = J > 0 ? (int64_t)(mu.size() / (size_t)J) : 0;
-                logmes.assign((size_t)M, 0.0);
-                if (partials)
-                    partials->assign(2 * (size_t)J * (size_t)M, 0.0);
-                if (terms)
-                    terms->assign((size_t)J * (size_t)M, 0.0);
+                _zeroed(M, logmes, partials, 2 * (size_t)J, terms, (size_t)J);
                 _eng.check(gpe_mes_values(_eng.get(), J, J > 0 ? (int)(ystar.size() / (size_t)J) : 0, ystar.data(), mu.data(), s.data(), M, logmes.data(),
-                               terms ? terms->data() : nullptr, partials ? partials->data() : nullptr),
+                               _data(terms), _data(partials)),
                     "gpe_mes_values");
             }
 
@@ -856,17 +777,12 @@ namespace limbo {
                     cmean->assign((size_t)S * (size_t)M, 0.0);
                 if (M == 0)
                     return 0;
-                auto ptr = [](std::vector<double>* v) { return v ? v->data() : nullptr; };
                 if (_joint_on_host(B + M))
-                    return _host_noisy_ei(candidates, baseline, Z, S, out, jitter, xi, lognei.data(), ptr(fplus), ptr(cvar), ptr(cmean));
+                    return _host_noisy_ei(candidates, baseline, Z, S, out, jitter, xi, lognei.data(), _data(fplus), _data(cvar), _data(cmean));
                 const std::vector<double> Xb = _joint_points(baseline), Xc = _joint_points(candidates);
-                std::vector<double> mb((size_t)B), ma((size_t)M);
-                for (int64_t i = 0; i < B; ++i)
-                    mb[(size_t)i] = _mean_function(baseline[(size_t)i], *this)(out);
-                for (int64_t m = 0; m < M; ++m)
-                    ma[(size_t)m] = _mean_function(candidates[(size_t)m], *this)(out);
+                const std::vector<double> mb = _mean_add(baseline, {out}), ma = _mean_add(candidates, {out});
                 return _eng.check(gpe_lognei_batch(_eng.get(), out, Xb.data(), B, mb.data(), jitter, Z.data(), S, xi, Xc.data(), M, ma.data(),
-                                      lognei.data(), ptr(fplus), nullptr, nullptr, ptr(cvar), ptr(cmean), S),
+                                      lognei.data(), _data(fplus), nullptr, nullptr, _data(cvar), _data(cmean), S),
                     "gpe_lognei_batch");
             }
 
@@ -1905,6 +1821,61 @@ namespace limbo {
                         if (a != b)
                             cov[b + M * a] = cov[a + M * b];
                     }
+            }
+            // ---- the marginal beliefs of a batch under some outputs (expected_hypervolume_improvement, log_constrained_ei,
+            // max_value_entropy) ----
+            static double* _data(std::vector<double>* v) { return v ? v->data() : nullptr; }
+            // are the outputs in range and distinct?
+            bool _outputs_ok(const std::vector<int>& outs) const
+            {
+                for (size_t j = 0; j < outs.size(); ++j) {
+                    if (outs[j] < 0 || outs[j] >= _dim_out)
+                        return false;
+                    for (size_t i = 0; i < j; ++i)
+                        if (outs[i] == outs[j])
+                            return false;
+                }
+                return true;
+            }
+            // size and zero what a call returns: one value per point, n_partials / n_terms columns where asked for
+            static void _zeroed(int64_t M, std::vector<double>& values, std::vector<double>* partials, size_t n_partials, std::vector<double>* terms,
+                size_t n_terms)
+            {
+                values.assign((size_t)M, 0.0);
+                if (partials)
+                    partials->assign(n_partials * (size_t)M, 0.0);
+                if (terms)
+                    terms->assign(n_terms * (size_t)M, 0.0);
+            }
+            // the host branch: query_batch(), then the means of outputs outs[j] and the standard deviation they share (the latent
+            // function's, or the observation's), both M x J column-major
+            void _beliefs_of(const std::vector<Eigen::VectorXd>& pts, const std::vector<int>& outs, bool observation, std::vector<double>& mu,
+                std::vector<double>& sd) const
+            {
+                const size_t M = pts.size(), J = outs.size();
+                const double noise = _kernel_function.noise();
+                Eigen::MatrixXd m;
+                Eigen::VectorXd s2;
+                query_batch(pts, m, s2);
+                mu.resize(M * J);
+                sd.resize(M * J);
+                for (size_t i = 0; i < M; ++i)
+                    for (size_t j = 0; j < J; ++j) {
+                        mu[i + M * j] = m(i, outs[j]);
+                        sd[i + M * j] = std::sqrt(observation ? s2(i) : std::max(s2(i) - noise, 0.0));
+                    }
+            }
+            // the device branch: the mean functor's outputs outs[j] at every point, M x J column-major
+            std::vector<double> _mean_add(const std::vector<Eigen::VectorXd>& pts, const std::vector<int>& outs) const
+            {
+                const size_t M = pts.size();
+                std::vector<double> add(M * outs.size());
+                for (size_t m = 0; m < M; ++m) {
+                    const Eigen::VectorXd mv = _mean_function(pts[m], *this);
+                    for (size_t j = 0; j < outs.size(); ++j)
+                        add[M * j + m] = mv(outs[j]);
+                }
+                return add;
             }
             // log_noisy_ei on the host: the baseline's covariance (B x B) and factor once, then the candidates in chunks of 512 — their
             // variances and the B x chunk cross-covariance alone, never the joint covariance of all B + M points.  No samples: the prior.

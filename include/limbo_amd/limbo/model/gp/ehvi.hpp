@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <limits>
 
+#include <limbo/model/gp/normal.hpp>
+
 namespace limbo_amd {
     namespace ehvi_host {
         struct Ev {
@@ -28,8 +30,8 @@ namespace limbo_amd {
             const double a = -std::fabs(z);
             double fm = 0.0, Q = 0.0, phi = 0.0;
             if (std::isfinite(a)) {
-                phi = std::exp(-0.5 * a * a) * 0.39894228040143267794;
-                Q = 0.5 * std::erfc(-a * 0.70710678118654752440);
+                phi = std::exp(-0.5 * a * a) * normal::inv_sqrt_2pi;
+                Q = 0.5 * std::erfc(-a * normal::inv_sqrt_2);
                 fm = std::fmax(phi + a * Q, 0.0);
             }
             return Ev{s * (z < 0.0 ? fm : z + fm), z < 0.0 ? Q : 1.0 - Q, phi};

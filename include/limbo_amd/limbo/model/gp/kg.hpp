@@ -10,6 +10,8 @@
 #include <limits>
 #include <vector>
 
+#include <limbo/model/gp/normal.hpp>
+
 namespace limbo_amd {
     namespace kg_host {
         /// f(-|z|) = phi(z) - |z| Phi(-|z|) >= 0
@@ -18,8 +20,8 @@ namespace limbo_amd {
             const double t = -std::fabs(z);
             if (!(t >= -DBL_MAX))
                 return t != t ? t : 0.0;
-            const double phi = std::exp(-0.5 * t * t) * 0.39894228040143267794;
-            const double Phi = 0.5 * std::erfc(-t * 0.70710678118654752440);
+            const double phi = std::exp(-0.5 * t * t) * normal::inv_sqrt_2pi;
+            const double Phi = 0.5 * std::erfc(-t * normal::inv_sqrt_2);
             return std::fmax(phi + t * Phi, 0.0);
         }
 

@@ -9,22 +9,17 @@
 #include <limits>
 #include <vector>
 
+#include <limbo/model/gp/normal.hpp>
+
 namespace limbo_amd {
     namespace mes_host {
-        constexpr double crossover = 3.0; // the continued fraction serves |g| > crossover
-        constexpr int depth = 60; // its partial quotients: 2.4e-17 of T is left at the crossover, less beyond
-        constexpr double log_sqrt_2pi = 0.91893853320467274178;
-        constexpr double inv_sqrt_2pi = 0.39894228040143267794;
-        constexpr double inv_sqrt_2 = 0.70710678118654752440;
+        using normal::crossover;
+        using normal::depth;
+        using normal::c2;
+        using normal::inv_sqrt_2;
+        using normal::inv_sqrt_2pi;
+        using normal::log_sqrt_2pi;
 
-        /// c2(x) = 2 / (x + 3 / (x + ...)), x > 0, every quotient positive: 1 / T = x + c2, T = 1 / R(x) - x with Mills' ratio R
-        inline double c2(double x)
-        {
-            double t = x;
-            for (int k = depth; k >= 3; --k)
-                t = x + (double)k / t;
-            return 2.0 / t;
-        }
         /// log t(g), t = g phi / (2 Phi) - log Phi, with r = t' / t <= 0.  g = -inf: (+inf, 0); g = +inf: (-inf, 0)
         inline void log_t(double g, double& lt, double& r)
         {

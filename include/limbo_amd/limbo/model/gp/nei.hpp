@@ -9,8 +9,8 @@
 #include <limits>
 #include <vector>
 
-#include <limbo/model/gp/cei.hpp>
 #include <limbo/model/gp/host_small.hpp>
+#include <limbo/model/gp/normal.hpp>
 
 namespace limbo_amd {
     namespace nei_host {
@@ -32,7 +32,7 @@ namespace limbo_amd {
                         term = d > 0.0 ? std::log(d) : (d != d ? d : -inf);
                     else {
                         double lh, rP, rp;
-                        cei_host::log_h(d / sd, lh, rP, rp);
+                        normal::log_h(d / sd, lh, rP, rp);
                         term = lsd + lh;
                     }
                     t[(size_t)s] = term;

@@ -89,6 +89,15 @@ def test_host_path_vs_reference_and_oracle(tmp_path, oracle_lib, kind, mean, P, 
     assert np.array_equal(b[:2], out["incremental"]["mu"].reshape(len(Q), P)[:2, 0]) and np.array_equal(b[2:], out["incremental"]["sigma"][:2])
 
 
+def test_acquisition_arguments_on_the_host():
+    """EHVI, CEI and MES through model::GP and the two-model forms with no candidates (everything comes back empty), output lists
+    with duplicates, out of range or naming the objective (std::invalid_argument), and the *_best arg-max: -1 without values,
+    the lowest index on exact ties, NaN never wins.  Host only: `test_host_path --arguments` says which check failed."""
+    subprocess.check_call(["make", "-s", "-C", str(ROOT / "tests" / "cpp"), "test_host_path"])
+    r = subprocess.run([str(DRIVER), "--arguments"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.splitlines()[-1] == "arguments failed 0", r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_host_path_under_asan_ubsan(tmp_path):
     """SURVEY §5 (the reference's memory / race checks are host-side tooling): the drop-in header set with
     -fsanitize=address,undefined (`make -C tests/cpp asan`).  The host path needs no GPU, so the instrumented driver runs

@@ -79,7 +79,7 @@ def build_driver(name):
     drv, src = CPP / name, CPP / (name + ".cpp")
     deps = [src, CPP / "query_grad_driver.hpp", ROOT / "limbo_amd" / "libgpengine.so", ROOT / "include" / "gpe_query_grad.h"]
     deps += [ROOT / "include" / "limbo_amd" / "limbo" / p for p in ("model/gp.hpp", "model/gp/query_grad.hpp", "acqui/ucb.hpp", "acqui/ei.hpp",
-                                                                  "acqui/afun_gradient.hpp", "opt/batch_search.hpp", "opt/batch_grad_search.hpp")]
+                                                                  "acqui/afun_gradient.hpp", "acqui/beliefs.hpp", "opt/batch_search.hpp", "opt/batch_grad_search.hpp")]
     if drv.exists() and all(drv.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return drv
     cmd = [os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-Wno-unused-variable", f"-I{ROOT}/include/limbo_amd",
