@@ -58,6 +58,7 @@
 #include <limbo/model/gp/pathwise.hpp>
 #include <limbo/model/gp/kg.hpp>
 #include <limbo/model/gp/ehvi.hpp>
+#include <limbo/model/gp/ehvi3.hpp>
 #include <limbo/model/gp/cei.hpp>
 #include <limbo/model/gp/mes.hpp>
 #include <limbo/model/gp/nei.hpp>
@@ -74,6 +75,7 @@
 #include "../../../gpe_batch_select.h"
 #include "../../../gpe_kg.h"
 #include "../../../gpe_ehvi.h"
+#include "../../../gpe_ehvi3.h"
 #include "../../../gpe_cei.h"
 #include "../../../gpe_mes.h"
 #include "../../../gpe_nei.h"
@@ -644,6 +646,49 @@ namespace limbo {
                 _eng.check(gpe_ehvi2_values(_eng.get(), front.data(), (int64_t)front.size() / 2, ref, mu1.data(), s1.data(), mu2.data(), s2.data(), M,
                                ehvi.data(), _data(partials)),
                     "gpe_ehvi2_values");
+            }
+
+            /// Addition (include/gpe_ehvi3.h, model/gp/ehvi3.hpp): the exact expected hypervolume improvement of every candidate
+            /// under THREE outputs of this model (outs: pairwise distinct, all maximised; they share sigma: limbo's GP with
+            /// dim_out = 3) over a prepared front (row-major n x 3: descending in the third of them, none dominated, all above
+            /// ref; limbo_amd::pareto_front3 makes one).  Means, sigma and `observation` as for two objectives above.  partials
+            /// (may be null): M x 6 column-major, d/d mu1, d/d s1, d/d mu2, d/d s2, d/d mu3, d/d s3.  The model is not changed.
+            /// On the model's home device; no samples (the prior), a host-resident model below the batch crossover and kernels
+            /// without device code: query_batch() and the host box sums of the same definition.
+            void expected_hypervolume_improvement3(const std::vector<Eigen::VectorXd>& candidates, const std::vector<double>& front,
+                const double* ref, const std::vector<int>& outs, bool observation, std::vector<double>& ehvi,
+                std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = candidates.size(), n = (int64_t)front.size() / 3;
+                if (front.size() % 3 != 0 || outs.size() != 3 || !_outputs_ok(outs) || !ref
+                    || gpe_ehvi3_values(nullptr, front.data(), n, ref, nullptr, nullptr, 0, nullptr, nullptr) != GPE_OK)
+                    throw std::invalid_argument("limbo_amd: expected_hypervolume_improvement3(): bad argument (include/gpe_ehvi3.h)");
+                _zeroed(M, ehvi, partials, 6, nullptr, 0);
+                if (M == 0)
+                    return;
+                if (_joint_on_host(M)) {
+                    std::vector<double> mu, sd;
+                    _beliefs_of(candidates, outs, observation, mu, sd);
+                    limbo_amd::ehvi3_host::Tables t;
+                    limbo_amd::ehvi3_host::tables(front.data(), n, ref, partials != nullptr, t);
+                    limbo_amd::ehvi3_host::box_sums(t, mu.data(), sd.data(), M, ehvi.data(), _data(partials));
+                    return;
+                }
+                const std::vector<double> Xc = _joint_points(candidates), add = _mean_add(candidates, outs);
+                _eng.check(gpe_ehvi3_batch(_eng.get(), outs.data(), Xc.data(), M, add.data(), observation ? _kernel_function.noise() : 0.0,
+                               front.data(), n, ref, ehvi.data(), _data(partials), nullptr, nullptr),
+                    "gpe_ehvi3_batch");
+            }
+            /// gpe_ehvi3_values through this model's engine handle (has_engine()): the box sums of beliefs the caller computed, mu
+            /// and s M x 3 column-major
+            void ehvi3_values(const std::vector<double>& front, const double* ref, const std::vector<double>& mu, const std::vector<double>& s,
+                std::vector<double>& ehvi, std::vector<double>* partials = nullptr) const
+            {
+                const int64_t M = (int64_t)mu.size() / 3;
+                _zeroed(M, ehvi, partials, 6, nullptr, 0);
+                _eng.check(gpe_ehvi3_values(_eng.get(), front.data(), (int64_t)front.size() / 3, ref, mu.data(), s.data(), M, ehvi.data(),
+                               _data(partials)),
+                    "gpe_ehvi3_values");
             }
 
             /// Addition (include/gpe_cei.h, model/gp/cei.hpp): the LOG of the constrained expected improvement of every candidate

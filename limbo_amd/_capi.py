@@ -25,6 +25,7 @@ REMOVE_AUTO, REMOVE_UPDATE, REMOVE_RECOMPUTE = range(3)  # include/gpe_remove.h:
 REMOVE_HOW = {"auto": 0, "update": 1, "recompute": 2}
 KG_MAX_ALTERNATIVES = 2048  # include/gpe_kg.h: GPE_KG_MAX_ALTERNATIVES
 EHVI_MAX_FRONT = 2048  # include/gpe_ehvi.h: GPE_EHVI_MAX_FRONT
+EHVI3_MAX_FRONT = 1024  # include/gpe_ehvi3.h: GPE_EHVI3_MAX_FRONT
 CEI_MAX_CONSTRAINTS = 16  # include/gpe_cei.h: GPE_CEI_MAX_CONSTRAINTS
 MES_MAX_OUTPUTS, MES_MAX_SAMPLES = 8, 1024  # include/gpe_mes.h: GPE_MES_MAX_OUTPUTS, GPE_MES_MAX_SAMPLES
 NEI_MAX_BASELINE, NEI_MAX_SAMPLES = 1024, 1024  # include/gpe_nei.h: GPE_NEI_MAX_BASELINE, GPE_NEI_MAX_SAMPLES
@@ -168,6 +169,12 @@ def _sig(lib, prefix):
             "ehvi2_values": [_vp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _i64, _dp, _dp],
             "ehvi2_batch": [_vp, C.c_int, C.c_int, _dp, _i64, _dp, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp],
             "ehvi_phase_ms": [_vp, _dp],
+            # include/gpe_ehvi3.h: the three-objective expected hypervolume improvement over a Pareto front
+            "ehvi3_front": [_dp, _i64, _dp, _dp, C.POINTER(_i64)],
+            "ehvi3_boxes": [_dp, _i64, _dp, C.c_int, _dp, _i64, C.POINTER(_i64)],
+            "ehvi3_values": [_vp, _dp, _i64, _dp, _dp, _dp, _i64, _dp, _dp],
+            "ehvi3_batch": [_vp, C.POINTER(C.c_int), _dp, _i64, _dp, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp],
+            "ehvi3_phase_ms": [_vp, _dp],
             # include/gpe_cei.h: constrained expected improvement in the log domain
             "logcei_values": [_vp, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _i64, _dp, _dp, _dp],
             "logcei_batch": [_vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), _dp, _dp, _i64, _dp, C.c_double,
@@ -240,6 +247,39 @@ def ehvi2_front(points, ref, check=True):
     rc = load_engine().fn("ehvi2_front")(_d(F), F.shape[0], _d(r), _d(out), C.byref(k))
     if check and rc < 0:
         raise EngineError(f"gpe_ehvi2_front failed: status {rc}")
+    return rc, out[: k.value].copy()
+
+
+def _front3_args(front, ref):
+    F = _c(np.asarray(front, dtype=np.float64).reshape(-1, 3))
+    r = _c(np.asarray(ref, dtype=np.float64).reshape(3))
+    return F, r
+
+
+def ehvi3_front(points, ref, check=True):
+    """gpe_ehvi3_front (include/gpe_ehvi3.h; host only, no handle): the Pareto front of `points` (n x 3, all objectives maximised)
+    above ref — dominated points, duplicates and points not above ref dropped, descending in f3, ties ascending in f1, then f2.
+    Returns (status, front (k, 3))."""
+    F, r = _front3_args(points, ref)
+    out = np.zeros((max(F.shape[0], 1), 3))
+    k = _i64(0)
+    rc = load_engine().fn("ehvi3_front")(_d(F), F.shape[0], _d(r), _d(out), C.byref(k))
+    if check and rc < 0:
+        raise EngineError(f"gpe_ehvi3_front failed: status {rc}")
+    return rc, out[: k.value].copy()
+
+
+def ehvi3_boxes(front, ref, axis, cap=None, check=True):
+    """gpe_ehvi3_boxes (host only, no handle): the box table of a prepared front (n x 3) for the height axis `axis`, rows
+    {l_a, u_a, l_b, u_b, h} with a < b the other two axes; also the prepared-front check.  cap: the rows there is room for (default
+    2n + 1, which always suffices).  Returns (status, boxes (k, 5))."""
+    F, r = _front3_args(front, ref)
+    cap = 2 * F.shape[0] + 1 if cap is None else int(cap)
+    out = np.zeros((max(cap, 1), 5))
+    k = _i64(0)
+    rc = load_engine().fn("ehvi3_boxes")(_d(F), F.shape[0], _d(r), int(axis), _d(out), cap, C.byref(k))
+    if check and rc < 0:
+        raise EngineError(f"gpe_ehvi3_boxes failed: status {rc}")
     return rc, out[: k.value].copy()
 
 
@@ -612,6 +652,45 @@ class Handle:
         """{solves, kernel, readback} of the last ehvi2_batch call in ms (set_profiling(True) first)."""
         ms = np.zeros(3)
         self._chk(self.lib.fn("ehvi_phase_ms")(self._h, _d(ms)), "ehvi_phase_ms")
+        return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
+
+    # -- the three-objective expected hypervolume improvement (include/gpe_ehvi3.h; HIP library only)
+    def ehvi3_values(self, front, ref, mu, s, want_partials=True, check=True):
+        """The box sums alone on host-supplied beliefs mu, s (M, 3; s: standard deviations) over a prepared front (n x 3;
+        ehvi3_front makes one); any handle serves.  Returns (status, ehvi (M), partials (M, 6: d/d mu1, s1, mu2, s2, mu3, s3) or
+        None).  check=False hands a negative GPE_ERR_* back instead of raising."""
+        F, r = _front3_args(front, ref)
+        mu, s = (_c(np.asarray(v, dtype=np.float64).reshape(-1, 3), "F") for v in (mu, s))
+        M = mu.shape[0]
+        assert s.shape[0] == M
+        ehvi = np.zeros(M)
+        part = np.zeros((M, 6), order="F") if want_partials else None
+        rc = self.lib.fn("ehvi3_values")(self._h, _d(F), F.shape[0], _d(r), _d(mu), _d(s), M, _d(ehvi), _d(part) if want_partials else None)
+        if check:
+            self._chk(rc, "ehvi3_values")
+        return rc, ehvi, part
+
+    def ehvi3_batch(self, Xc, front, ref, outs=(0, 1, 2), mean_add=None, var_add=0.0, want=("ehvi", "partials", "mu", "var"), check=True):
+        """The expected hypervolume improvement of every row of Xc under the handle's three outputs `outs`, which share sigma.
+        mean_add: (M, 3) added to k^T alpha, or None; var_add: added to the clamped variance (0: the latent function).  Returns
+        (status, ehvi (M), partials (M, 6), mu (M, 3), var (M)), None for what `want` leaves out."""
+        Xc = _c(Xc).reshape(-1, self.D)
+        M = Xc.shape[0]
+        F, r = _front3_args(front, ref)
+        o = (C.c_int * 3)(*[int(v) for v in outs])
+        ma = _c(np.asarray(mean_add, dtype=np.float64).reshape(M, 3), "F") if mean_add is not None else None
+        out = {"ehvi": np.zeros(M), "partials": np.zeros((M, 6), order="F"), "mu": np.zeros((M, 3), order="F"), "var": np.zeros(M)}
+        ptr = [_d(out[k]) if k in want else None for k in ("ehvi", "partials", "mu", "var")]
+        rc = self.lib.fn("ehvi3_batch")(self._h, o, _d(Xc), M, _d(ma) if ma is not None else None, float(var_add), _d(F), F.shape[0], _d(r),
+                                        *ptr)
+        if check:
+            self._chk(rc, "ehvi3_batch")
+        return (rc,) + tuple(out[k] if k in want else None for k in ("ehvi", "partials", "mu", "var"))
+
+    def ehvi3_phase_ms(self):
+        """{solves, kernel, readback} of the last ehvi3_batch call in ms (set_profiling(True) first)."""
+        ms = np.zeros(3)
+        self._chk(self.lib.fn("ehvi3_phase_ms")(self._h, _d(ms)), "ehvi3_phase_ms")
         return dict(zip(("solves", "kernel", "readback"), ms.tolist()))
 
     # -- constrained expected improvement in the log domain (include/gpe_cei.h; HIP library only)

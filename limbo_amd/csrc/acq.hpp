@@ -1,11 +1,11 @@
 // acq.hpp — what the acquisition functions on a fitted model share on the host: the knowledge gradient (kg.hpp), the expected
-// hypervolume improvement (ehvi.hpp), constrained expected improvement (cei.hpp), max-value entropy search (mes.hpp) and noisy
+// hypervolume improvement of two and of three objectives (ehvi.hpp, ehvi3.hpp), constrained expected improvement (cei.hpp), max-value entropy search (mes.hpp) and noisy
 // expected improvement (nei.hpp).  A part of engine.hip's translation unit (included there, once, behind query.hpp, joint.hpp and
-// select.hpp, whose helpers it builds on, and in front of the five).
+// select.hpp, whose helpers it builds on, and in front of the six).
 //   cand_chunk_max, kValuesChunk      how many candidates go at once: through the model, and as beliefs handed over by the caller
 //   cand_chunk                        a candidate chunk's head, solve and variance
 //   cross_cov                         c = k(Xa, Xc) - Z_a^T Z_c of a resident point set with a candidate chunk
-//   acq_batch(AcqCall, launch)        the fused call of an acquisition over marginal beliefs (ehvi, cei, mes)
+//   acq_batch(AcqCall, launch)        the fused call of an acquisition over marginal beliefs (ehvi, ehvi3, cei, mes)
 //   acq_values(AcqValues, launch)     the same kernel on beliefs from the host
 //   outs_ok                           output indices in [0, P), pairwise distinct
 // An acquisition is a description and a function that launches its kernel for one chunk (AcqChunk): nothing here knows which.

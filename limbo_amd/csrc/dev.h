@@ -572,6 +572,20 @@ struct EhviArgs {
 };
 void launch_ehvi2(hipStream_t s, const EhviArgs& q);
 
+// ---- the three-objective expected hypervolume improvement (ehvi3.hip; include/gpe_ehvi3.h) ------------------------------
+// ehvi[m] and, ntab == 3, the six partials (column c at partials + c ldp) of candidate m < M; one wave each.  tables (device): ntab
+// box tables one behind the other, rows {l_a, u_a, l_b, u_b, h}, nb[t] rows each; table 0: height axis 2 (the value and the partials
+// of objective 3), tables 1 and 2 (ntab == 3): height axes 0 and 1.  Beliefs 0 .. 2 of b: the objectives.
+struct Ehvi3Args {
+    const double* tables;
+    int ntab, nb[3];
+    BeliefArgs b;
+    int64_t M;
+    double *ehvi, *partials;
+    int64_t ldp;
+};
+void launch_ehvi3(hipStream_t s, const Ehvi3Args& q);
+
 // ---- constrained expected improvement in the log domain (cei.hip; include/gpe_cei.h) ------------------------------------
 // logcei[m] and, where asked, terms (column j at terms + j ldt, j <= C) and partials (column j at partials + j ldp, j < 2 + 2 C) of
 // candidate m < M; one thread each.  Belief 0 of b: the objective (with_ei == 0: not read), 1 .. C: the constraints.

@@ -25,6 +25,7 @@
 #include "../../include/gpe_batch_select.h"
 #include "../../include/gpe_kg.h"
 #include "../../include/gpe_ehvi.h"
+#include "../../include/gpe_ehvi3.h"
 #include "../../include/gpe_cei.h"
 #include "../../include/gpe_mes.h"
 #include "../../include/gpe_nei.h"
@@ -33,11 +34,13 @@
 #include "carve.h" // (the typed scratch carver of query.hpp: a template, so outside the extern "C" block below)
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
+#include <limits>
 #include <atomic>
 #include <chrono>
 #include <map>
@@ -47,6 +50,7 @@
 #include <sys/file.h>
 #include <sys/stat.h>
 #include <thread>
+#include <tuple>
 #include <unistd.h>
 #include <mutex>
 #include <string>
@@ -248,6 +252,7 @@ struct gpe_ctx {
     double joint_ms[4] = {0, 0, 0, 0}; // the last joint call's Z, Sigma, factorisation (host clock) and draws, ms, while profiling is on
     double kg_ms[4] = {0, 0, 0, 0}; // the last gpe_kg_batch call's alternatives' pass, candidates' solves with the cross-covariance, envelopes and read-back, ms, while profiling is on
     double ehvi_ms[3] = {0, 0, 0}; // the last gpe_ehvi2_batch call's solves, strip kernel and read-back, ms, while profiling is on
+    double ehvi3_ms[3] = {0, 0, 0}; // the last gpe_ehvi3_batch call's solves, box kernel and read-back, ms, while profiling is on
     double cei_ms[3] = {0, 0, 0}; // the last gpe_logcei_batch call's solves, kernel and read-back, ms, while profiling is on
     double mes_ms[3] = {0, 0, 0}; // the last gpe_mes_batch call's solves, kernel and read-back, ms, while profiling is on
     double nei_ms[5] = {0, 0, 0, 0, 0}; // the last gpe_lognei_batch call's baseline pass with Sigma_b, factorisation with the draws, candidates' solves with the cross-covariance, conditioning, kernel with the read-back, ms, while profiling is on
@@ -1312,6 +1317,7 @@ int gpe_query_batch_cross(gpe_handle c, const double* Ks, int64_t M, double* kta
 #include "acq.hpp"    // what the acquisition functions below share: the chunk rule, a chunk's steps, the two pipelines
 #include "kg.hpp"     // the knowledge gradient over a finite alternative set (include/gpe_kg.h)
 #include "ehvi.hpp"   // the two-objective expected hypervolume improvement over a Pareto front (include/gpe_ehvi.h)
+#include "ehvi3.hpp"  // the three-objective expected hypervolume improvement: front, box tables, calls (include/gpe_ehvi3.h)
 #include "cei.hpp"    // constrained expected improvement in the log domain (include/gpe_cei.h)
 #include "mes.hpp"    // max-value entropy search in the log domain (include/gpe_mes.h)
 #include "nei.hpp"    // noisy expected improvement in the log domain (include/gpe_nei.h)
