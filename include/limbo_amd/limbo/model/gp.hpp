@@ -22,7 +22,8 @@
 // the host matrices _matrixL / _alpha and compute(), add_sample(), recompute(), compute_log_lik() and the single-point query(),
 // mu(), sigma() never touch the device: one core's O(n^2) call is cheaper than a launch plus a PCIe round trip (the BO inner
 // loop of bayes_opt/boptimizer.hpp:148-161 on models of 10..200 samples).  Whatever has no host form — K^-1, the gradients,
-// the LOO objectives, the batched hyper-parameter objectives — moves the model to the device for good (_host_off); a large
+// the LOO objectives, the batched hyper-parameter objectives — moves the model to the device for good (limbo_amd::Residency,
+// gp/residency.hpp, keeps where it lives); a large
 // query_batch() answers from a device copy of the host model that is refreshed when the host model has changed.
 //
 // Additions (not in the reference): query_batch() — the batched acquisition path of SURVEY.md
@@ -54,6 +55,8 @@
 #include <limbo/mean/constant.hpp>
 #include <limbo/mean/data.hpp>
 #include <limbo/model/gp/host_small.hpp>
+#include <limbo/model/gp/replicas.hpp>
+#include <limbo/model/gp/residency.hpp>
 #include <limbo/model/gp/query_grad.hpp>
 #include <limbo/model/gp/pathwise.hpp>
 #include <limbo/model/gp/kg.hpp>
@@ -80,82 +83,6 @@
 #include "../../../gpe_mes.h"
 #include "../../../gpe_nei.h"
 
-namespace limbo_amd {
-    /// RAII owner of one engine handle (one GP resident on the device)
-    class Engine {
-    public:
-        explicit Engine(int device) : _h(nullptr), _device(device) {}
-        Engine(const Engine& o) : Engine(o, o._device) {}
-        /// deep copy onto `device` (peer copy over xGMI when it differs from o's)
-        Engine(const Engine& o, int device) : _h(nullptr), _device(device)
-        {
-            if (o._h)
-                check(gpe_clone_to(o._h, _device, &_h), "gpe_clone_to");
-        }
-        Engine(Engine&& o) noexcept : _h(o._h), _device(o._device) { o._h = nullptr; }
-        Engine& operator=(Engine&& o) noexcept
-        {
-            if (this != &o) {
-                reset();
-                _h = o._h;
-                _device = o._device;
-                o._h = nullptr;
-            }
-            return *this;
-        }
-        /// move the GP to another device of the node (no-op when it is there already)
-        void set_device(int device)
-        {
-            if (device == _device)
-                return;
-            if (_h) {
-                gpe_handle n = nullptr;
-                check(gpe_clone_to(_h, device, &n), "gpe_clone_to");
-                gpe_destroy(_h);
-                _h = n;
-            }
-            _device = device;
-        }
-        Engine& operator=(const Engine& o)
-        {
-            if (this != &o) {
-                reset();
-                _device = o._device;
-                if (o._h)
-                    check(gpe_clone(o._h, &_h), "gpe_clone");
-            }
-            return *this;
-        }
-        ~Engine() { reset(); }
-        void reset()
-        {
-            if (_h)
-                gpe_destroy(_h);
-            _h = nullptr;
-        }
-        gpe_handle get()
-        {
-            if (!_h)
-                check(gpe_create(_device, &_h), "gpe_create");
-            return _h;
-        }
-        gpe_handle peek() const { return _h; }
-        int device() const { return _device; }
-        /// negative status = API/HIP error: loud; positive = non-positive pivot: returned
-        int check(int rc, const char* what) const
-        {
-            if (rc < 0)
-                throw std::runtime_error(std::string("limbo_amd engine: ") + what + " failed (" + std::to_string(rc) + "): "
-                    + (_h ? gpe_last_error(_h) : "no MI355X / libgpengine.so not usable"));
-            return rc;
-        }
-
-    private:
-        gpe_handle _h;
-        int _device;
-    };
-} // namespace limbo_amd
-
 namespace limbo {
     namespace model {
         template <typename Params, typename KernelFunction = kernel::MaternFiveHalves<Params>, typename MeanFunction = mean::Data<Params>, typename HyperParamsOptimizer = gp::NoLFOpt<Params>>
@@ -171,7 +98,7 @@ namespace limbo {
 
             /// the same onto another device of the node (addition: how the parallel policies spread independent GPs)
             GP(const GP& o, int device)
-                : _dim_in(o._dim_in), _dim_out(o._dim_out), _kernel_function(o._kernel_function), _mean_function(o._mean_function), _samples(o._samples), _observations(o._observations), _mean_vector(o._mean_vector), _obs_mean(o._obs_mean), _alpha(o._alpha), _mean_observation(o._mean_observation), _kernel(o._kernel), _inv_kernel(o._inv_kernel), _matrixL(o._matrixL), _log_lik(o._log_lik), _log_loo_cv(o._log_loo_cv), _inv_kernel_updated(o._inv_kernel_updated), _hp_optimize(o._hp_optimize), _eng(o._eng, device), _status(o._status), _L_stale(o._L_stale), _alpha_stale(o._alpha_stale), _Kinv_stale(o._Kinv_stale), _dev_theta(o._dev_theta), _dev_noise(o._dev_noise), _dev_kernel_ok(o._dev_kernel_ok), _host_mode(o._host_mode), _host_off(o._host_off) {}
+                : _dim_in(o._dim_in), _dim_out(o._dim_out), _kernel_function(o._kernel_function), _mean_function(o._mean_function), _samples(o._samples), _observations(o._observations), _mean_vector(o._mean_vector), _obs_mean(o._obs_mean), _alpha(o._alpha), _mean_observation(o._mean_observation), _kernel(o._kernel), _inv_kernel(o._inv_kernel), _matrixL(o._matrixL), _log_lik(o._log_lik), _log_loo_cv(o._log_loo_cv), _inv_kernel_updated(o._inv_kernel_updated), _hp_optimize(o._hp_optimize), _eng(o._eng, device), _status(o._status), _res(o._res.for_copy()) {}
 
             /// device this GP lives on / move it (additions)
             int device() const { return _eng.device(); }
@@ -197,14 +124,7 @@ namespace limbo {
                 assert(observations.size() != 0);
                 assert(samples.size() == observations.size());
 
-                if (_dim_in != (int)samples[0].size()) {
-                    _dim_in = samples[0].size();
-                    _kernel_function = KernelFunction(_dim_in);
-                }
-                if (_dim_out != (int)observations[0].size()) {
-                    _dim_out = observations[0].size();
-                    _mean_function = MeanFunction(_dim_out);
-                }
+                _adopt_dims((int)samples[0].size(), (int)observations[0].size());
                 _samples = samples;
                 _observations.resize(observations.size(), _dim_out);
                 for (int i = 0; i < (int)_observations.rows(); ++i)
@@ -212,7 +132,7 @@ namespace limbo {
                         _observations(i, p) = observations[i](p);
                 _update_mean_observation();
                 this->_compute_obs_mean();
-                _data_on_device = false;
+                _res.return_to_full_path();
                 if (compute_kernel)
                     this->_compute_full_kernel();
             }
@@ -224,16 +144,8 @@ namespace limbo {
             /// O(n^2) reallocation per sample)
             void add_sample(const Eigen::VectorXd& sample, const Eigen::VectorXd& observation)
             {
-                if (_samples.empty()) {
-                    if (_dim_in != (int)sample.size()) {
-                        _dim_in = sample.size();
-                        _kernel_function = KernelFunction(_dim_in);
-                    }
-                    if (_dim_out != (int)observation.size()) {
-                        _dim_out = observation.size();
-                        _mean_function = MeanFunction(_dim_out);
-                    }
-                }
+                if (_samples.empty())
+                    _adopt_dims((int)sample.size(), (int)observation.size());
                 else {
                     assert((int)sample.size() == _dim_in);
                     assert((int)observation.size() == _dim_out);
@@ -256,16 +168,8 @@ namespace limbo {
                 const int64_t q = (int64_t)samples.size();
                 if (q == 0)
                     return;
-                if (_samples.empty()) {
-                    if (_dim_in != (int)samples[0].size()) {
-                        _dim_in = samples[0].size();
-                        _kernel_function = KernelFunction(_dim_in);
-                    }
-                    if (_dim_out != (int)observations[0].size()) {
-                        _dim_out = observations[0].size();
-                        _mean_function = MeanFunction(_dim_out);
-                    }
-                }
+                if (_samples.empty())
+                    _adopt_dims((int)samples[0].size(), (int)observations[0].size());
                 for (int64_t i = 0; i < q; ++i) {
                     assert((int)samples[i].size() == _dim_in);
                     assert((int)observations[i].size() == _dim_out);
@@ -301,12 +205,7 @@ namespace limbo {
                     _obs_mean.resize(0, _dim_out);
                     _alpha.resize(0, _dim_out);
                     _matrixL.resize(0, 0);
-                    _host_mode = false;
-                    _data_on_device = false; // (the next samples go through the full path)
-                    _dev_shadow_ok = false;
-                    _L_stale = _alpha_stale = false;
-                    _Kinv_stale = true;
-                    _inv_kernel_updated = false;
+                    _emptied();
                     release_query_replicas();
                     return;
                 }
@@ -379,7 +278,7 @@ namespace limbo {
                     return;
                 }
                 std::vector<double> kta((size_t)(M * _dim_out)), var((size_t)M);
-                if (_host_mode && M * (int64_t)_samples.size() < (int64_t)limbo_amd::host_batch_crossover())
+                if (_res.on_host() && M * (int64_t)_samples.size() < (int64_t)limbo_amd::host_batch_crossover())
                     for (int64_t m = 0; m < M; ++m) { // a handful of points on a small model: still cheaper here
                         _host_query(points[m], &kta[(size_t)m], M, &var[(size_t)m]);
                     }
@@ -420,7 +319,7 @@ namespace limbo {
                 if (kind == limbo_amd::KIND_HOST_K)
                     throw std::logic_error("limbo_amd: query_grad_batch(): this kernel has no device code, hence no derivative in the query point");
                 std::vector<double> kta((size_t)(M * P)), var((size_t)M), dkta((size_t)(M * D * P)), dvar((size_t)(M * D));
-                if (_host_mode && M * n < (int64_t)limbo_amd::host_batch_crossover())
+                if (_res.on_host() && M * n < (int64_t)limbo_amd::host_batch_crossover())
                     _host_query_grad(points, kta.data(), var.data(), dkta.data(), dvar.data());
                 else {
                     const std::vector<double> Xq = _joint_points(points);
@@ -635,7 +534,7 @@ namespace limbo {
             /// Does this model hold an engine handle a caller's own beliefs can be scored through (ehvi2_values)?
             bool has_engine() const
             {
-                return !_host_mode && _eng.peek() != nullptr && limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K;
+                return !_res.on_host() && _eng.peek() != nullptr && limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K;
             }
             /// gpe_ehvi2_values through this model's engine handle (has_engine()): the strip sums of beliefs the caller computed
             void ehvi2_values(const std::vector<double>& front, const double* ref, const std::vector<double>& mu1, const std::vector<double>& s1,
@@ -785,7 +684,7 @@ namespace limbo {
             /// no bound for a model that lives on the host
             int64_t joint_max_points() const
             {
-                if (_samples.size() == 0 || _host_mode || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K)
+                if (_samples.size() == 0 || _res.on_host() || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K)
                     return std::numeric_limits<int64_t>::max();
                 int64_t m = 0;
                 _eng.check(gpe_joint_max_points(_eng.get(), &m), "gpe_joint_max_points");
@@ -854,11 +753,8 @@ namespace limbo {
                     || (!E.empty() && (int64_t)E.size() < n * S * P))
                     throw std::runtime_error("limbo_amd: sample_paths(): Omega0, phase, W or E is smaller than features x draws x dim_out asks for");
                 auto mean = [this](const Eigen::VectorXd& v) { return Eigen::VectorXd(_mean_function(v, *this)); };
-                if (n == 0 || _host_mode) {
-                    std::vector<double> X((size_t)(n * D));
-                    for (int64_t i = 0; i < n; ++i)
-                        for (int d = 0; d < D; ++d)
-                            X[(size_t)(i * D + d)] = _samples[(size_t)i](d);
+                if (n == 0 || _res.on_host()) {
+                    const std::vector<double> X = _pack(_samples, 0, (size_t)n);
                     limbo_amd::pathwise::HostPaths h;
                     h.make(kind, hp.data(), nk, D, P, X.data(), n, n ? matrixL().data() : nullptr, _obs_mean.data(), _kernel_function.noise(), R, S,
                         Omega0.data(), phase.data(), W.data(), E.empty() ? nullptr : E.data());
@@ -929,14 +825,13 @@ namespace limbo {
             {
                 _need_device();
                 _status_or(_eng.check(gpe_compute_inv_kernel(_eng.get()), "gpe_compute_inv_kernel"));
-                _Kinv_stale = true;
-                _inv_kernel_updated = true;
+                _Kinv_on_device();
             }
 
             /// gp.hpp:267-282
             double compute_log_lik()
             {
-                if (_host_mode) { // gp.hpp:267-282, the P-quirk kept: log det and n log 2 pi are not multiplied by dim_out
+                if (_res.on_host()) { // gp.hpp:267-282, the P-quirk kept: log det and n log 2 pi are not multiplied by dim_out
                     const int64_t n = _samples.size();
                     long double logdet = 0.0L;
                     for (int64_t i = 0; i < n; ++i)
@@ -964,8 +859,7 @@ namespace limbo {
                 if (limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K) {
                     _push_kernel();
                     _eng.check(gpe_log_lik_grad(_eng.get(), grad.data(), T, Params::kernel::optimize_noise() ? 1 : 0), "gpe_log_lik_grad");
-                    _inv_kernel_updated = true; // the device computed and cached K^-1 (gp.hpp:289-291)
-                    _Kinv_stale = true;
+                    _Kinv_on_device(); // the device computed and cached K^-1 (gp.hpp:289-291)
                     return grad;
                 }
                 // kernels without device code: w = alpha alpha^T - K^-1 from the device, d k / d theta from the functor
@@ -1016,8 +910,7 @@ namespace limbo {
                 _need_device();
                 double v = 0.0;
                 _eng.check(gpe_log_loo_cv(_eng.get(), &v), "gpe_log_loo_cv");
-                _inv_kernel_updated = true; // gp.hpp:342-344
-                _Kinv_stale = true;
+                _Kinv_on_device(); // gp.hpp:342-344
                 _log_loo_cv = v;
                 return _log_loo_cv;
             }
@@ -1033,16 +926,14 @@ namespace limbo {
                 if (limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K) {
                     _push_kernel();
                     _eng.check(gpe_log_loo_cv_grad(_eng.get(), grad.data(), T, Params::kernel::optimize_noise() ? 1 : 0), "gpe_log_loo_cv_grad");
-                    _inv_kernel_updated = true;
-                    _Kinv_stale = true;
+                    _Kinv_on_device();
                     return grad;
                 }
                 // kernels without device code: W from the device, d k / d theta from the functor
                 const size_t n = _samples.size();
                 Eigen::MatrixXd W(n, n);
                 _eng.check(gpe_get_loo_weights(_eng.get(), W.data(), (int64_t)n), "gpe_get_loo_weights");
-                _inv_kernel_updated = true;
-                _Kinv_stale = true;
+                _Kinv_on_device();
                 for (size_t i = 0; i < n; ++i)
                     for (size_t j = 0; j <= i; ++j) {
                         Eigen::VectorXd g = _kernel_function.grad(_samples[i], _samples[j], i, j);
@@ -1058,21 +949,21 @@ namespace limbo {
             const Eigen::MatrixXd& matrixL() const
             {
                 std::lock_guard<std::mutex> lk(_mirror_mu);
-                if (_L_stale && !_host_mode) {
+                if (_res.L_stale()) {
                     const int64_t n = _samples.size();
                     _matrixL.resize(n, n);
                     _eng.check(gpe_get_L(_eng.get(), _matrixL.data(), n), "gpe_get_L");
-                    _L_stale = false;
+                    _res.L_fetched();
                 }
                 return _matrixL;
             }
             const Eigen::MatrixXd& alpha() const
             {
                 std::lock_guard<std::mutex> lk(_mirror_mu);
-                if (_alpha_stale && !_host_mode) {
+                if (_res.alpha_stale()) {
                     _alpha.resize(_samples.size(), _dim_out);
                     _eng.check(gpe_get_alpha(_eng.get(), _alpha.data()), "gpe_get_alpha");
-                    _alpha_stale = false;
+                    _res.alpha_fetched();
                 }
                 return _alpha;
             }
@@ -1126,16 +1017,13 @@ namespace limbo {
                 _samples.clear();
                 archive.load(_samples, "samples");
                 archive.load(_observations, "observations");
-                _dim_in = _samples[0].size();
-                _kernel_function = KernelFunction(_dim_in);
+                _adopt_dims((int)_samples[0].size(), (int)_observations.cols(), true);
                 if (_kernel_function.h_params_size() > 0) {
                     Eigen::VectorXd h_params;
                     archive.load(h_params, "kernel_params");
                     assert(h_params.size() == (int)_kernel_function.h_params_size());
                     _kernel_function.set_h_params(h_params);
                 }
-                _dim_out = _observations.cols();
-                _mean_function = MeanFunction(_dim_out);
                 if (_mean_function.h_params_size() > 0) {
                     Eigen::VectorXd h_params;
                     archive.load(h_params, "mean_params");
@@ -1143,7 +1031,7 @@ namespace limbo {
                     _mean_function.set_h_params(h_params);
                 }
                 _update_mean_observation();
-                _data_on_device = false;
+                _res.return_to_full_path();
                 if (recompute)
                     this->recompute(true, true);
                 else { // trust the stored factor: upload L and alpha (the block inverses are rebuilt on the device)
@@ -1151,19 +1039,15 @@ namespace limbo {
                     archive.load(_matrixL, "matrixL");
                     archive.load(_alpha, "alpha");
                     if (_use_host((int64_t)_samples.size())) { // a small model stays where single-point calls are cheapest
-                        _host_mode = true;
-                        _dev_shadow_ok = false;
-                        _L_stale = _alpha_stale = false;
-                        _inv_kernel_updated = false;
+                        _res.alpha_recomputed_on_host(); // (the stored alpha and factor are the host model)
+                        _host_factor(true);
                         return;
                     }
-                    _host_mode = false;
                     _push_data();
                     _push_kernel();
                     _eng.check(gpe_set_L(_eng.get(), _matrixL.data(), _matrixL.rows()), "gpe_set_L");
                     _eng.check(gpe_set_alpha(_eng.get(), _alpha.data()), "gpe_set_alpha");
-                    _L_stale = _alpha_stale = false;
-                    _inv_kernel_updated = false;
+                    _factor_uploaded();
                 }
             }
 
@@ -1194,35 +1078,43 @@ namespace limbo {
             // ---- device side -------------------------------------------------------------------
             mutable limbo_amd::Engine _eng;
             int _status = 0;
-            mutable bool _L_stale = true, _alpha_stale = true, _Kinv_stale = true;
-            bool _data_on_device = false;
-            Eigen::VectorXd _dev_theta; // hyper-parameters last sent to the device
-            double _dev_noise = -1.0;
-            bool _dev_kernel_ok = false;
-            mutable std::mutex _mirror_mu;
-            // ---- host side (round 4): a small model's factor and alpha are _matrixL / _alpha themselves ----
-            bool _host_mode = false;            // the host matrices are the model (the device holds nothing current)
-            bool _host_off = false;             // this object has needed the device for something with no host form: it stays there
-            mutable bool _dev_shadow_ok = false; // (host mode) the device copy that serves large query_batch() calls is current
-            mutable Eigen::VectorXd _shadow_hp;   // ... and the kernel hyper-parameters / noise it was given
-            mutable double _shadow_noise = -1.0;
-            // ---- query replicas (round 6): one deep copy of the device model per OTHER visible device, made lazily by the first
-            // large query_batch() and valid while the engine's epoch (gpe_epoch) stands still; never copied with the GP
-            mutable std::vector<limbo_amd::Engine> _replicas;
-            mutable uint64_t _replica_epoch = 0;
-            mutable std::mutex _replica_mu;
+            mutable limbo_amd::Residency _res; // where the model lives, which mirrors are current (gp/residency.hpp); mutable: the mirrors
+            mutable std::mutex _mirror_mu;     // and the shadow of a host model are filled from const calls
+            mutable limbo_amd::QueryReplicas _replicas; // (gp/replicas.hpp) never copied with the GP
 
-            bool _use_host(int64_t n) const { return !_host_off && n < (int64_t)limbo_amd::min_n_for_gpu<Params>(); }
+            bool _use_host(int64_t n) const { return _res.use_host(n, (int64_t)limbo_amd::min_n_for_gpu<Params>()); }
             /// everything without a host form: the model moves to the device and stays there
             void _need_device()
             {
-                _host_off = true;
-                if (_host_mode) {
-                    _host_mode = false;
-                    _data_on_device = false;
-                    if (!_samples.empty())
-                        _compute_full_kernel();
-                }
+                if (_res.leave_host_for_good() && !_samples.empty())
+                    _compute_full_kernel();
+            }
+
+            // ---- the events that move _inv_kernel_updated (the reference's member) together with _res: one site each ----
+            void _host_factor(bool built) // gp.hpp:570 / :602
+            {
+                built ? _res.factor_built_on_host() : _res.factor_updated_on_host();
+                _inv_kernel_updated = false;
+            }
+            void _device_factor() // gp.hpp:570 / :602
+            {
+                _res.factor_changed_on_device();
+                _inv_kernel_updated = false;
+            }
+            void _factor_uploaded()
+            {
+                _res.factor_uploaded();
+                _inv_kernel_updated = false;
+            }
+            void _Kinv_on_device()
+            {
+                _res.Kinv_produced_on_device();
+                _inv_kernel_updated = true;
+            }
+            void _emptied()
+            {
+                _res.emptied();
+                _inv_kernel_updated = false;
             }
 
             void _swap(GP& o)
@@ -1245,21 +1137,32 @@ namespace limbo {
                 std::swap(_inv_kernel_updated, o._inv_kernel_updated);
                 std::swap(_eng, o._eng);
                 std::swap(_status, o._status);
-                std::swap(_L_stale, o._L_stale);
-                std::swap(_alpha_stale, o._alpha_stale);
-                std::swap(_Kinv_stale, o._Kinv_stale);
-                std::swap(_data_on_device, o._data_on_device);
-                std::swap(_dev_theta, o._dev_theta);
-                std::swap(_dev_noise, o._dev_noise);
-                std::swap(_dev_kernel_ok, o._dev_kernel_ok);
-                std::swap(_host_mode, o._host_mode);
-                std::swap(_host_off, o._host_off);
-                std::swap(_dev_shadow_ok, o._dev_shadow_ok);
-                std::swap(_shadow_hp, o._shadow_hp); // (the flag never travels without what it vouches for)
-                std::swap(_shadow_noise, o._shadow_noise);
-                _replicas.clear(); // (replicas belong to a handle; both handles changed hands)
+                std::swap(_res, o._res); // (whole: a swap, unlike a copy, keeps "data on the device" and the shadow with their handle)
+                _replicas.clear();       // (replicas belong to a handle; both handles changed hands)
                 o._replicas.clear();
-                _replica_epoch = o._replica_epoch = 0;
+            }
+
+            void _adopt_dims(int dim_in, int dim_out, bool always = false)
+            {
+                if (always || _dim_in != dim_in) {
+                    _dim_in = dim_in;
+                    _kernel_function = KernelFunction(_dim_in);
+                }
+                if (always || _dim_out != dim_out) {
+                    _dim_out = dim_out;
+                    _mean_function = MeanFunction(_dim_out);
+                }
+            }
+
+            /// points [lo, hi) of pts as row-major doubles, the engine's layout
+            std::vector<double> _pack(const std::vector<Eigen::VectorXd>& pts, size_t lo, size_t hi) const
+            {
+                std::vector<double> X((hi - lo) * (size_t)_dim_in);
+                for (size_t i = lo; i < hi; ++i) {
+                    assert((int)pts[i].size() == _dim_in);
+                    std::copy(pts[i].data(), pts[i].data() + _dim_in, X.begin() + (i - lo) * (size_t)_dim_in);
+                }
+                return X;
             }
 
             void _status_or(int rc)
@@ -1296,30 +1199,27 @@ namespace limbo {
                 }
             }
 
+            /// X and obs_mean to the device (const: a host model's shadow is filled from const calls; they do not raise data_pushed)
+            void _send_data() const
+            {
+                const std::vector<double> X = _pack(_samples, 0, _samples.size());
+                _eng.check(gpe_set_data(_eng.get(), X.data(), (int64_t)_samples.size(), _dim_in, _obs_mean.data(), _dim_out), "gpe_set_data");
+            }
             void _push_data()
             {
-                const int64_t n = _samples.size();
-                std::vector<double> X((size_t)(n * _dim_in));
-                for (int64_t i = 0; i < n; ++i)
-                    for (int d = 0; d < _dim_in; ++d)
-                        X[(size_t)(i * _dim_in + d)] = _samples[i](d);
-                _eng.check(gpe_set_data(_eng.get(), X.data(), n, _dim_in, _obs_mean.data(), _dim_out), "gpe_set_data");
-                _data_on_device = true;
-                _dev_kernel_ok = false;
+                _send_data();
+                _res.data_pushed();
             }
 
             /// kernel.hpp:116-123 on the device: log-space parameters (without the noise entry) + sigma_n^2
-            void _push_kernel()
+            void _send_kernel(const Eigen::VectorXd& hp, double noise) const
             {
                 constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
-                if (kind == limbo_amd::KIND_HOST_K) {
-                    _eng.check(gpe_set_kernel(_eng.get(), kind, nullptr, 0, _kernel_function.noise()), "gpe_set_kernel");
-                    return;
-                }
-                Eigen::VectorXd hp = _kernel_function.h_params();
-                const int nk = (int)hp.size() - (Params::kernel::optimize_noise() ? 1 : 0);
-                _eng.check(gpe_set_kernel(_eng.get(), kind, hp.data(), nk, _kernel_function.noise()), "gpe_set_kernel");
+                const bool functor_built = kind == limbo_amd::KIND_HOST_K; // (K and k* come from the host: no parameters to send)
+                const int nk = functor_built ? 0 : (int)hp.size() - (Params::kernel::optimize_noise() ? 1 : 0);
+                _eng.check(gpe_set_kernel(_eng.get(), kind, functor_built ? nullptr : hp.data(), nk, noise), "gpe_set_kernel");
             }
+            void _push_kernel() { _send_kernel(_kernel_function.h_params(), _kernel_function.noise()); }
 
             /// gp.hpp:550-571: K -> L -> alpha, all on the device
             void _compute_full_kernel()
@@ -1328,7 +1228,7 @@ namespace limbo {
                     _host_full_kernel();
                     return;
                 }
-                _host_mode = false;
+                _res.moved_to_device();
                 _stage_full_kernel();
                 _commit_full_kernel(_eng.check(gpe_compute(_eng.get()), "gpe_compute"));
             }
@@ -1343,13 +1243,8 @@ namespace limbo {
                     for (int64_t i = j; i < n; ++i)
                         L[i + j * n] = _kernel_function(_samples[i], _samples[j], i, j);
                 _status = limbo_amd::host_small::llt_lower(L, n, n);
-                _host_mode = true;
-                _data_on_device = false;
-                _dev_shadow_ok = false;
                 _host_alpha();
-                _L_stale = false;
-                _Kinv_stale = true;
-                _inv_kernel_updated = false; // gp.hpp:570
+                _host_factor(true);
             }
             /// gp.hpp:605-611 on the host
             void _host_alpha()
@@ -1358,8 +1253,7 @@ namespace limbo {
                 _alpha = _obs_mean;
                 limbo_amd::host_small::solve_lower(_matrixL.data(), n, n, _alpha.data(), _dim_out, n);
                 limbo_amd::host_small::solve_lower_t(_matrixL.data(), n, n, _alpha.data(), _dim_out, n);
-                _alpha_stale = false;
-                _dev_shadow_ok = false;
+                _res.alpha_recomputed_on_host();
             }
             /// gp.hpp:613-632 on the host: kta[p * ldk] = k*^T alpha_p, *var = k(v, v) - |L^-1 k*|^2 (before mean / clamp / noise)
             void _host_query(const Eigen::VectorXd& v, double* kta, int64_t ldk, double* var) const
@@ -1396,49 +1290,31 @@ namespace limbo {
                 // so do the host loop and, now, this copy — whichever side of host_batch_crossover a batch falls on.
                 const Eigen::VectorXd hp = _kernel_function.h_params();
                 const double nz = _kernel_function.noise();
-                const bool same_kernel = _shadow_noise == nz && _shadow_hp.size() == hp.size()
-                    && std::equal(hp.data(), hp.data() + hp.size(), _shadow_hp.data());
-                if (_dev_shadow_ok && same_kernel)
+                std::vector<double> hpv(hp.data(), hp.data() + hp.size());
+                if (_res.shadow_current(hpv, nz))
                     return;
-                const int64_t n = _samples.size();
-                constexpr int kind = limbo_amd::device_kernel<KernelFunction>::kind;
-                if (!_dev_shadow_ok) {
-                    std::vector<double> X((size_t)(n * _dim_in));
-                    for (int64_t i = 0; i < n; ++i)
-                        for (int d = 0; d < _dim_in; ++d)
-                            X[(size_t)(i * _dim_in + d)] = _samples[i](d);
-                    _eng.check(gpe_set_data(_eng.get(), X.data(), n, _dim_in, _obs_mean.data(), _dim_out), "gpe_set_data");
-                }
-                if (kind == limbo_amd::KIND_HOST_K)
-                    _eng.check(gpe_set_kernel(_eng.get(), kind, nullptr, 0, nz), "gpe_set_kernel");
-                else {
-                    const int nk = (int)hp.size() - (Params::kernel::optimize_noise() ? 1 : 0);
-                    _eng.check(gpe_set_kernel(_eng.get(), kind, hp.data(), nk, nz), "gpe_set_kernel");
-                }
+                if (!_res.shadow_valid())
+                    _send_data();
+                _send_kernel(hp, nz);
                 // (the factor goes up with every kernel change too: gpe_set_L also refreshes the Lambda^T x rows of SE-ARD with
                 // Lambda columns, which depend on the hyper-parameters — n < min_n_for_gpu: a few hundred KB)
                 _eng.check(gpe_set_L(_eng.get(), _matrixL.data(), _matrixL.rows()), "gpe_set_L");
                 _eng.check(gpe_set_alpha(_eng.get(), _alpha.data()), "gpe_set_alpha");
-                _shadow_hp = hp;
-                _shadow_noise = nz;
-                _dev_shadow_ok = true;
+                _res.shadow_refreshed(std::move(hpv), nz);
             }
 
         public:
             /// Addition: this model lives on the host (below Params::gpu::min_n_for_gpu samples, nothing device-only asked yet)
-            bool host_resident() const { return _host_mode && _use_host((int64_t)_samples.size()); }
+            bool host_resident() const { return _res.on_host() && _use_host((int64_t)_samples.size()); }
 
             /// Additions: the two halves of `_compute_full_kernel` around the device factorisation, so that a caller
             /// holding several independent GPs (model::MultiGP: one per output, multi_gp.hpp:124-126) can run all their
             /// factorisations as ONE batched launch sequence (`compute_full_kernels_batched` -> gpe_batch_compute).
             void _stage_full_kernel()
             {
-                if (_host_mode) { // (the batched callers: this object computes on the device from here on)
-                    _host_off = true;
-                    _host_mode = false;
-                    _data_on_device = false;
-                }
-                if (!_data_on_device)
+                if (_res.on_host()) // (the batched callers: this object computes on the device from here on)
+                    _res.leave_host_for_good();
+                if (!_res.data_on_device())
                     _push_data();
                 else
                     _eng.check(gpe_set_obs_mean(_eng.get(), _obs_mean.data()), "gpe_set_obs_mean");
@@ -1457,8 +1333,7 @@ namespace limbo {
             void _commit_full_kernel(int status)
             {
                 _status = status;
-                _L_stale = _alpha_stale = _Kinv_stale = true;
-                _inv_kernel_updated = false; // gp.hpp:570
+                _device_factor();
             }
             /// `_compute_full_kernel()` of every GP in `gps` (data already set: compute(samples, obs, false) or an earlier
             /// compute): GPs on the same device are stepped together by gpe_batch_compute (one launch sequence,
@@ -1511,12 +1386,11 @@ namespace limbo {
                 const bool on = Params::kernel::optimize_noise();
                 std::vector<int> devs;
                 for (GP* g : gps) {
-                    if (g->_host_mode || !g->_host_off) { // lock-step restarts / outputs run on the device
-                        g->_host_off = true;
-                        g->_host_mode = false;
-                        g->_data_on_device = false;
+                    if (g->_res.on_host() || !g->_res.pinned()) { // lock-step restarts / outputs run on the device, the data re-sent
+                        g->_res.leave_host_for_good();
+                        g->_res.return_to_full_path();
                     }
-                    if (!g->_data_on_device)
+                    if (!g->_res.data_on_device())
                         g->_push_data();
                     if (std::find(devs.begin(), devs.end(), g->device()) == devs.end())
                         devs.push_back(g->device());
@@ -1547,7 +1421,7 @@ namespace limbo {
                         g->_log_lik = lk[q];
                         liks[mine[q]] = lk[q];
                         if (want_grad) {
-                            g->_inv_kernel_updated = true; // the device computed and cached K^-1 (gp.hpp:289-291)
+                            g->_Kinv_on_device(); // the device computed and cached K^-1 (gp.hpp:289-291)
                             grads[mine[q]] = Eigen::VectorXd::Zero(T);
                             for (int t = 0; t < T; ++t)
                                 grads[mine[q]](t) = gr[q * T + t];
@@ -1558,152 +1432,115 @@ namespace limbo {
 
         protected:
 
-            /// gp.hpp:573-603
-            void _compute_incremental_kernel()
+            /// One update of the factor after _samples changed from n0 rows (the factor _matrixL / the device still holds): on the
+            /// host (host_step builds the new _matrixL; alpha follows) when the model lives there and stays there; through the full
+            /// path, which decides where the model lives, when it crosses the threshold, its K is functor-built, its data is not
+            /// on the device or it was empty; else on the device (device_step: the engine call, its status returned).
+            template <typename HostStep, typename DeviceStep>
+            void _update_factor(int64_t n0, HostStep host_step, DeviceStep device_step)
             {
-                const int64_t n1 = _samples.size(); // samples including the new one
-                if (_host_mode && _use_host(n1) && n1 >= 2 && (int64_t)_matrixL.rows() == n1 - 1) {
-                    // gp.hpp:573-603 on the host: one more row of L, then alpha (gp.hpp:599)
-                    const int64_t n = n1 - 1;
-                    std::vector<double> kcol((size_t)n), row((size_t)n1);
+                const int64_t n1 = _samples.size();
+                if (_res.on_host() && _use_host(n1) && n0 >= 1 && (int64_t)_matrixL.rows() == n0) {
+                    host_step();
+                    _host_alpha();
+                    _host_factor(false);
+                    return;
+                }
+                if (_res.on_host() || _use_host(n1) || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K
+                    || !_res.data_on_device() || n0 == 0) {
+                    _res.return_to_full_path();
+                    _compute_full_kernel();
+                    return;
+                }
+                _push_kernel();
+                _status_or(device_step());
+                _device_factor();
+            }
+
+            /// gp.hpp:573-603 on the host for the rows n0 .. of _samples: L moves into the final-size matrix once, the rows follow
+            /// one by one (host_small::append_row)
+            void _host_append_rows(int64_t n0)
+            {
+                const int64_t n1 = _samples.size();
+                Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
+                for (int64_t j = 0; j < n0; ++j) {
+                    const double* src = _matrixL.data() + j * n0;
+                    double* dst = L2.data() + j * n1;
+                    for (int64_t i = j; i < n0; ++i)
+                        dst[i] = src[i];
+                }
+                std::vector<double> kcol((size_t)n1), row((size_t)n1);
+                int bad = 0;
+                for (int64_t n = n0; n < n1; ++n) {
                     for (int64_t i = 0; i < n; ++i)
                         kcol[(size_t)i] = _kernel_function(_samples[i], _samples[n], i, n);
                     const double knn = _kernel_function(_samples[n], _samples[n], n, n);
-                    const int bad = limbo_amd::host_small::append_row(_matrixL.data(), n, n, kcol.data(), knn, row.data());
-                    Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
-                    for (int64_t j = 0; j < n; ++j) {
-                        const double* src = _matrixL.data() + j * n;
-                        double* dst = L2.data() + j * n1;
-                        for (int64_t i = j; i < n; ++i)
-                            dst[i] = src[i];
-                        dst[n] = row[(size_t)j];
-                    }
-                    L2.data()[n + n * n1] = row[(size_t)n];
-                    _matrixL = L2;
-                    if (bad)
-                        _status = bad;
-                    _host_alpha();
-                    _L_stale = false;
-                    _Kinv_stale = true;
-                    _inv_kernel_updated = false; // gp.hpp:602
-                    return;
+                    const int b = limbo_amd::host_small::append_row(L2.data(), n, n1, kcol.data(), knn, row.data());
+                    for (int64_t j = 0; j <= n; ++j)
+                        L2.data()[n + j * n1] = row[(size_t)j];
+                    if (b && !bad)
+                        bad = b;
                 }
-                if (_host_mode || _use_host(n1)) { // crossing the threshold (or the first samples): the full path decides where
-                    _data_on_device = false;
-                    _compute_full_kernel();
-                    return;
-                }
-                if (limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K || !_data_on_device || _samples.size() == 1) {
-                    _data_on_device = false;
-                    _compute_full_kernel(); // first sample / functor-built K: full path
-                    return;
-                }
-                _push_kernel();
-                _status_or(_eng.check(gpe_add_sample(_eng.get(), _samples.back().data(), _dim_in, _obs_mean.data(), _dim_out), "gpe_add_sample"));
-                _L_stale = _alpha_stale = _Kinv_stale = true;
-                _inv_kernel_updated = false; // gp.hpp:602
+                _matrixL = std::move(L2);
+                if (bad)
+                    _status = bad;
             }
 
-            /// gp.hpp:573-603 for the rows n0 .. of _samples at once (add_samples); the cases are _compute_incremental_kernel's
+            /// gp.hpp:573-603: one row appended to L (add_sample: the engine's single-row path)
+            void _compute_incremental_kernel()
+            {
+                const int64_t n0 = (int64_t)_samples.size() - 1;
+                _update_factor(n0, [&] { _host_append_rows(n0); }, [&] {
+                    return _eng.check(gpe_add_sample(_eng.get(), _samples.back().data(), _dim_in, _obs_mean.data(), _dim_out), "gpe_add_sample");
+                });
+            }
+
+            /// ... and the rows n0 .. of _samples at once (add_samples: the engine's blocked path, also for one row)
             void _compute_incremental_block(int64_t n0)
             {
-                const int64_t n1 = _samples.size();
-                if (_host_mode && _use_host(n1) && n0 >= 1 && (int64_t)_matrixL.rows() == n0) {
-                    // on the host: L moves into the final-size matrix once, the rows follow one by one, then alpha once
-                    Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
-                    for (int64_t j = 0; j < n0; ++j) {
-                        const double* src = _matrixL.data() + j * n0;
-                        double* dst = L2.data() + j * n1;
-                        for (int64_t i = j; i < n0; ++i)
-                            dst[i] = src[i];
-                    }
-                    std::vector<double> kcol((size_t)n1), row((size_t)n1);
-                    int bad = 0;
-                    for (int64_t n = n0; n < n1; ++n) {
-                        for (int64_t i = 0; i < n; ++i)
-                            kcol[(size_t)i] = _kernel_function(_samples[i], _samples[n], i, n);
-                        const double knn = _kernel_function(_samples[n], _samples[n], n, n);
-                        const int b = limbo_amd::host_small::append_row(L2.data(), n, n1, kcol.data(), knn, row.data());
-                        for (int64_t j = 0; j <= n; ++j)
-                            L2.data()[n + j * n1] = row[(size_t)j];
-                        if (b && !bad)
-                            bad = b;
-                    }
-                    _matrixL = std::move(L2);
-                    if (bad)
-                        _status = bad;
-                    _host_alpha();
-                    _L_stale = false;
-                    _Kinv_stale = true;
-                    _inv_kernel_updated = false; // gp.hpp:602
-                    return;
-                }
-                if (_host_mode || _use_host(n1) || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K || !_data_on_device
-                    || n0 == 0) {
-                    // crossing the host / device threshold, a functor-built K, an empty model: the full path decides where
-                    _data_on_device = false;
-                    _compute_full_kernel();
-                    return;
-                }
-                _push_kernel();
-                const int64_t q = n1 - n0;
-                std::vector<double> X((size_t)(q * _dim_in));
-                for (int64_t i = 0; i < q; ++i)
-                    for (int d = 0; d < _dim_in; ++d)
-                        X[(size_t)(i * _dim_in + d)] = _samples[(size_t)(n0 + i)](d);
-                _status_or(_eng.check(gpe_add_samples(_eng.get(), X.data(), q, _dim_in, _obs_mean.data(), _dim_out), "gpe_add_samples"));
-                _L_stale = _alpha_stale = _Kinv_stale = true;
-                _inv_kernel_updated = false; // gp.hpp:602
+                _update_factor(n0, [&] { _host_append_rows(n0); }, [&] {
+                    const std::vector<double> X = _pack(_samples, (size_t)n0, _samples.size());
+                    return _eng.check(gpe_add_samples(_eng.get(), X.data(), (int64_t)_samples.size() - n0, _dim_in, _obs_mean.data(), _dim_out), "gpe_add_samples");
+                });
             }
 
-            /// The factor after the rows R (ascending) left a model of n0 samples (remove_samples); the cases are
-            /// _compute_incremental_block's
+            /// The factor after the rows R (ascending) left a model of n0 samples (remove_samples): on the host the same column
+            /// sweep on _matrixL
             void _compute_removed(const std::vector<int64_t>& R, int64_t n0)
             {
                 const int64_t n1 = _samples.size(), q = (int64_t)R.size();
-                if (_host_mode && _use_host(n1) && (int64_t)_matrixL.rows() == n0) {
-                    // on the host: the same column sweep on _matrixL, then alpha
-                    Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
-                    limbo_amd::host_small::remove_rows(_matrixL.data(), n0, n0, R.data(), q, L2.data(), n1);
-                    _matrixL = std::move(L2);
-                    _host_alpha();
-                    _L_stale = false;
-                    _Kinv_stale = true;
-                    _inv_kernel_updated = false;
-                    return;
-                }
-                if (_host_mode || _use_host(n1) || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K || !_data_on_device) {
-                    // crossing the host / device threshold, a functor-built K, data not on the device: the full path decides where
-                    _data_on_device = false;
-                    _compute_full_kernel();
-                    return;
-                }
-                _push_kernel();
-                _eng.check(gpe_remove_samples(_eng.get(), R.data(), q, _obs_mean.data(), _dim_out, GPE_REMOVE_AUTO), "gpe_remove_samples");
-                _L_stale = _alpha_stale = _Kinv_stale = true;
-                _inv_kernel_updated = false;
+                _update_factor(n0,
+                    [&] {
+                        Eigen::MatrixXd L2 = Eigen::MatrixXd::Zero(n1, n1);
+                        limbo_amd::host_small::remove_rows(_matrixL.data(), n0, n0, R.data(), q, L2.data(), n1);
+                        _matrixL = std::move(L2);
+                    },
+                    [&] {
+                        _eng.check(gpe_remove_samples(_eng.get(), R.data(), q, _obs_mean.data(), _dim_out, GPE_REMOVE_AUTO), "gpe_remove_samples");
+                        return 0; // (the update reports no pivot: last_status() keeps the factorisation's)
+                    });
             }
 
             /// gp.hpp:605-611 with the existing factor
             void _compute_alpha()
             {
-                if (_host_mode) {
+                if (_res.on_host()) {
                     _host_alpha();
                     return;
                 }
                 _eng.check(gpe_update_alpha(_eng.get(), _obs_mean.data()), "gpe_update_alpha");
-                _alpha_stale = true;
+                _res.alpha_changed_on_device();
             }
 
             const Eigen::MatrixXd& _host_Kinv() const
             {
-                assert(!_host_mode); // (K^-1 only exists on the device: compute_inv_kernel() moved the model there)
+                assert(!_res.on_host()); // (K^-1 only exists on the device: compute_inv_kernel() moved the model there)
                 std::lock_guard<std::mutex> lk(_mirror_mu);
-                if (_Kinv_stale) {
+                if (_res.Kinv_stale()) {
                     const int64_t n = _samples.size();
                     _inv_kernel.resize(n, n);
                     _eng.check(gpe_get_Kinv(_eng.get(), _inv_kernel.data(), n), "gpe_get_Kinv");
-                    _Kinv_stale = false;
+                    _res.Kinv_fetched();
                 }
                 return _inv_kernel;
             }
@@ -1712,23 +1549,18 @@ namespace limbo {
             void _query_many(const std::vector<Eigen::VectorXd>& pts, double* kta, double* var) const
             {
                 const int64_t M = pts.size(), n = _samples.size();
-                if (_host_mode)
-                    _sync_device_shadow();
                 if (limbo_amd::device_kernel<KernelFunction>::kind != limbo_amd::KIND_HOST_K) {
-                    std::vector<double> Xq((size_t)(M * _dim_in));
-                    for (int64_t m = 0; m < M; ++m) {
-                        assert((int)pts[m].size() == _dim_in);
-                        for (int d = 0; d < _dim_in; ++d)
-                            Xq[(size_t)(m * _dim_in + d)] = pts[m](d);
-                    }
-                if (!_host_mode && limbo_amd::multi_device_query_min() > 0 && M >= (int64_t)limbo_amd::multi_device_query_min()
-                    && limbo_amd::visible_devices() > 1 && limbo_amd::param_device<Params>::get() < 0) {
-                    _query_over_devices(Xq.data(), M, kta, var);
+                    const std::vector<double> Xq = _joint_points(pts);
+                    // one GP's batch over ALL visible devices (gp/replicas.hpp); not when Params::gpu::device() pins the model
+                    if (!_res.on_host() && limbo_amd::multi_device_query_min() > 0 && M >= (int64_t)limbo_amd::multi_device_query_min()
+                        && limbo_amd::visible_devices() > 1 && limbo_amd::param_device<Params>::get() < 0)
+                        _replicas.query(_eng, limbo_amd::visible_devices(), Xq.data(), M, _dim_in, _dim_out, kta, var);
+                    else
+                        _eng.check(gpe_query_batch(_eng.get(), Xq.data(), M, kta, var), "gpe_query_batch");
                     return;
                 }
-                _eng.check(gpe_query_batch(_eng.get(), Xq.data(), M, kta, var), "gpe_query_batch");
-                    return;
-                }
+                if (_res.on_host())
+                    _sync_device_shadow();
                 // functor-built cross kernel (gp.hpp:626-632), solves on the device
                 std::vector<double> Ks((size_t)(n * M)), zz((size_t)M);
                 for (int64_t m = 0; m < M; ++m)
@@ -1739,93 +1571,25 @@ namespace limbo {
                     for (int64_t m = 0; m < M; ++m)
                         var[m] = _kernel_function(pts[m], pts[m]) - zz[(size_t)m];
             }
-            /// One GP's batch over ALL visible devices (missing 3; the reference's parallel query: multi_gp.hpp:191-195,
-            /// tools/parallel.hpp:138-201 — TBB tasks over host cores there): device d answers a contiguous slice of the points
-            /// on its own replica of the model (gpe_clone_to: a peer copy over xGMI, made once per state of the model — the
-            /// engine's epoch — and kept), one host thread per device, no collective: every slice lands in the caller's
-            /// arrays.  Batched queries pick their kernels from N alone, so a point's answer does not depend on the slice it
-            /// fell into: the result is bitwise the one-device answer.  Not used when Params::gpu::device() pins the model.
-            void _query_over_devices(const double* Xq, int64_t M, double* kta, double* var) const
-            {
-                std::lock_guard<std::mutex> lk(_replica_mu);
-                const int ndev = limbo_amd::visible_devices(), own = _eng.device();
-                uint64_t ep = 0;
-                _eng.check(gpe_epoch(_eng.get(), &ep), "gpe_epoch");
-                if ((int)_replicas.size() != ndev - 1 || _replica_epoch != ep) {
-                    _replicas.clear();
-                    _replicas.reserve((size_t)(ndev - 1));
-                    for (int d = 0; d < ndev; ++d)
-                        if (d != own)
-                            _replicas.emplace_back(_eng, d);
-                    _replica_epoch = ep;
-                }
-                const int P = _dim_out, D = _dim_in;
-                auto lo_of = [&](int k) { return (int64_t)k * (M / ndev) + std::min<int64_t>(k, M % ndev); }; // (parallel.py: row_slice)
-                std::vector<std::string> errs((size_t)ndev);
-                auto work = [&](int k, limbo_amd::Engine* e) {
-                    try {
-                        const int64_t lo = lo_of(k), m = lo_of(k + 1) - lo;
-                        if (m <= 0)
-                            return;
-                        if (P == 1 || !kta) {
-                            e->check(gpe_query_batch(e->get(), Xq + lo * D, m, kta ? kta + lo : nullptr, var ? var + lo : nullptr), "gpe_query_batch");
-                            return;
-                        }
-                        std::vector<double> kl((size_t)(m * P)); // kta is [point + M output]: a slice is not contiguous in it
-                        e->check(gpe_query_batch(e->get(), Xq + lo * D, m, kl.data(), var ? var + lo : nullptr), "gpe_query_batch");
-                        for (int p = 0; p < P; ++p)
-                            std::copy(kl.begin() + (size_t)(m * p), kl.begin() + (size_t)(m * (p + 1)), kta + lo + M * p);
-                    }
-                    catch (const std::exception& ex) {
-                        errs[(size_t)k] = ex.what();
-                    }
-                };
-                std::vector<std::thread> th;
-                int slot = 1; // slice 0 is the model's own device (this thread), slices 1.. the replicas in device order
-                for (auto& r : _replicas)
-                    th.emplace_back(work, slot++, &r);
-                work(0, &_eng);
-                for (auto& t : th)
-                    t.join();
-                for (auto& e : errs)
-                    if (!e.empty())
-                        throw std::runtime_error(e);
-            }
         public:
             /// Addition: give the per-device query replicas back (device memory: one copy of the model on every other device)
-            void release_query_replicas() const
-            {
-                std::lock_guard<std::mutex> lk(_replica_mu);
-                _replicas.clear();
-                _replica_epoch = 0;
-            }
+            void release_query_replicas() const { _replicas.clear(); }
             /// Addition (tests): how many devices the last large query_batch() was dealt over (1 + replicas alive)
-            int query_devices() const
-            {
-                std::lock_guard<std::mutex> lk(_replica_mu);
-                return 1 + (int)_replicas.size();
-            }
+            int query_devices() const { return _replicas.devices(); }
         protected:
             // ---- the joint posterior (query_joint, sample) ----
             bool _joint_on_host(int64_t M) const
             {
                 if (_samples.size() == 0 || limbo_amd::device_kernel<KernelFunction>::kind == limbo_amd::KIND_HOST_K)
                     return true;
-                return _host_mode && M * (int64_t)_samples.size() < (int64_t)limbo_amd::host_batch_crossover();
+                return _res.on_host() && M * (int64_t)_samples.size() < (int64_t)limbo_amd::host_batch_crossover();
             }
             // row-major points for the engine (a host-resident model first refreshes its device copy)
             std::vector<double> _joint_points(const std::vector<Eigen::VectorXd>& pts) const
             {
-                if (_host_mode)
+                if (_res.on_host())
                     _sync_device_shadow();
-                const int64_t M = pts.size();
-                std::vector<double> Xq((size_t)(M * _dim_in));
-                for (int64_t m = 0; m < M; ++m) {
-                    assert((int)pts[m].size() == _dim_in);
-                    for (int d = 0; d < _dim_in; ++d)
-                        Xq[(size_t)(m * _dim_in + d)] = pts[m](d);
-                }
-                return Xq;
+                return _pack(pts, 0, pts.size());
             }
             // kta[m + M p], cov (M x M, column-major) on the host: the prior without samples, else from matrixL() and alpha()
             void _host_joint(const std::vector<Eigen::VectorXd>& pts, double* kta, double* cov, double jitter) const
@@ -2073,7 +1837,7 @@ namespace limbo {
             }
             void _query_one(const Eigen::VectorXd& v, Eigen::VectorXd* kta, double* var) const
             {
-                if (_host_mode) {
+                if (_res.on_host()) {
                     if (kta)
                         kta->resize(_dim_out);
                     _host_query(v, kta ? kta->data() : nullptr, 1, var);

@@ -12,8 +12,8 @@ into --bin (default: a temporary directory; --no-build: take the programs that a
 Every driver's input is written by the test modules' own run_driver from their own problem generators (dropin_problem, with_steps
 and their siblings in tests/test_*_host.py): inside those modules `subprocess` is replaced by a recorder that runs the program
 built here in place of the test's, under its own time limit.  One line per case: name, exit status, sha256 of stdout.  The first
-case that does not end with status 0, or whose model did not live where the case wants it (the drivers' host_resident line), ends
-the run.  --sanitize builds with -fsanitize=address,undefined as `make -C tests/cpp asan` does (other bits: the statuses count, not
+case that does not end with status 0, or whose model did not live where the case wants it (the host_resident lines of the drivers
+that print them: all 1 or all 0, or the per-step sequence of the residency walk), ends the run.  --sanitize builds with -fsanitize=address,undefined as `make -C tests/cpp asan` does (other bits: the statuses count, not
 the hashes): stand-alone programs on the host cases, on a machine's CPU only.
 
 --cases host: below Params::gpu::min_n_for_gpu with the host tests' HOST_ENV, nothing touches the device.  --cases device: n = 300
@@ -36,7 +36,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 DRIVERS = ("test_cei_dropin", "test_mes_dropin", "test_ehvi_dropin", "test_nei_dropin", "test_kg_dropin", "test_batch_select_dropin",
-           "test_query_grad_host", "test_query_grad_dropin")
+           "test_query_grad_host", "test_query_grad_dropin", "test_host_path", "test_add_samples", "test_remove_samples", "test_residency_walk")
 DEVICE_ENV = {"LIMBO_AMD_MIN_N_FOR_GPU": "0"}
 RUN_LIMIT_S = 120
 AB_CASES = ("cei.c2.obs1.steps", "mes.p2.obs1.steps")
@@ -72,6 +72,10 @@ class Recorder:
         env.setdefault("UBSAN_OPTIONS", "halt_on_error=1:print_stacktrace=1")
         return env
 
+    @staticmethod
+    def check_call(*a, **kw):  # (a test module's `make`: the programs are built here)
+        return 0
+
     def run(self, argv, **kw):
         self.last = (argv, kw)
         self.result = subprocess.run(self.command(argv), capture_output=True, text=True, env=self.environment(kw))
@@ -84,8 +88,13 @@ class Recorder:
         return time.perf_counter() - t0, r.returncode
 
 
-def cases(path):
-    """(name, module, call): call(run_driver, tmp_path) writes the input and runs the driver"""
+# host_resident after every step of tests/cpp/test_residency_walk (tests/test_residency_walk.py, tests/test_gpu_residency_walk.py).  A
+# model pinned to the device by compute_inv_kernel() stays pinned when it is emptied, so the refill of `cross` stays on the device.
+WALK = {"host": "1 1 1 1 1 1 1 1 1 0 1", "cross": "1 1 0 1 1 1 1 0 0 0 0 0 0", "device": "0 0 0 0 0 0 0 0 0 0 0 0 0"}
+
+
+def cases(path, rec):
+    """(name, module, call[, host_resident lines expected]): call(run_driver, tmp_path) writes the input and runs the driver"""
     import numpy as np
 
     from tests import test_batch_select as BS
@@ -148,6 +157,31 @@ def cases(path):
         case = QG.dropin_problem(kind, n, 3, 2 if kind == QG.O.SE_ARD else 1, M, 40 + kind)
         out.append((f"query_grad.kind{kind}", QG, lambda run, tmp, c=case: run(drv, "grad", QG.grad_case_text(*c), tmp, qenv)))
     out.append(("query_grad.search", QG, lambda run, tmp: run(drv, "search", QG.search_case_text(n=n), tmp, qenv)))
+
+    # the factor's life: compute / add_sample / add_samples / remove_samples and the walk across the host / device boundaries
+    from tests import test_add_samples_host as AS
+    from tests import test_host_path as HP
+
+    none = []  # (these drivers print no host_resident line)
+    if host:
+        for kind, mean, P, Dh, n0, n1 in HP.CASES:  # the problems of test_host_path_vs_reference_and_oracle
+            rng = np.random.default_rng(100 * kind + 10 * mean + P)
+            Xh = rng.uniform(-1, 1, size=(n1, Dh))
+            Yh = np.stack([np.cos((p + 1.5) * Xh.sum(axis=1)) + 0.3 * Xh[:, 0] for p in range(P)], axis=1) + 0.05 * rng.normal(size=(n1, P))
+            Qh = np.concatenate([rng.uniform(-1, 1, size=(4, Dh)), Xh[:2]])
+            out.append((f"host_path.k{kind}.m{mean}.p{P}", HP, lambda run, tmp, a=(kind, mean, Xh, Yh, n0, Qh): HP._run(tmp, *a), none))
+        out.append(("host_path.arguments", HP, lambda run, tmp: HP.test_acquisition_arguments_on_the_host(), none))
+    for kind, mean, P, Da, n0, n1 in (AS.CASES if host else [(0, 0, 1, 6, 300, 340)]):
+        Xa, Ya, Qa = AS.problem(kind, mean, P, Da, n1)
+
+        def add(run, tmp, a=(kind, mean, Xa, Ya, n0, Qa)):
+            AS.write_input(tmp / "in.txt", *a)
+            rec.run(["test_add_samples", tmp / "in.txt"] + ([] if host else ["device"]))
+
+        out.append((f"add_samples.k{kind}.m{mean}.p{P}", AS, add, none))
+    out.append(("remove_samples", AS, lambda run, tmp: rec.run(["test_remove_samples"] + ([] if host else ["device"])), none))
+    for mode in (["host"] if host else ["cross", "device"]):
+        out.append((f"walk.{mode}", AS, lambda run, tmp, m=mode: rec.run(["test_residency_walk", m]), WALK[mode].split()))
     return out
 
 
@@ -168,21 +202,22 @@ def main():
             build(Path(a.include).resolve(), bindir, a.sanitize)
         rec = Recorder(bindir)
         timings = []
-        for name, mod, call in cases(a.cases):
+        for name, mod, call, *expect in cases(a.cases, rec):
             mod.subprocess = rec
             if hasattr(mod, "DRIVER"):
                 mod.build_driver = lambda d=mod.DRIVER: d  # (the recorder takes the program of that name from bindir)
             tmp = Path(scratch) / name
             tmp.mkdir()
             try:
-                call(mod.run_driver, tmp)
+                call(getattr(mod, "run_driver", None), tmp)
             except AssertionError:
                 pass  # (run_driver's own check of the status: the line below says it)
             r = rec.result
             print(f"{a.cases}/{name}", r.returncode, hashlib.sha256(r.stdout.encode()).hexdigest(), flush=True)
             # the path the case is about was the one taken: the drivers say where the model lived
             where = [w for ln in r.stdout.splitlines() if ln.startswith("host_resident") for w in ln.split()[1:]]
-            if r.returncode != 0 or not where or set(where) != {"1" if a.cases == "host" else "0"} or "runtime error" in r.stderr:
+            lived = where == expect[0] if expect else bool(where) and set(where) == {"1" if a.cases == "host" else "0"}
+            if r.returncode != 0 or not lived or "runtime error" in r.stderr:
                 print(f"case {name}: status {r.returncode}, host_resident {where}; stopping\n{r.stderr[-2000:]}", file=sys.stderr)
                 return 1
             if a.ab and name in AB_CASES:
